@@ -14,16 +14,27 @@ loop, N = 50, K = 4 Legendre collocation, fp64, B = 512 seeded COLD starts per G
 One step = one lockstep iteration of the batched solver over its batch. The solve starts from the
 cold starts; lockstep iterations [W, W + K) are timed (device synchronised at both ends; the
 first W are the warmup); value = instance-iterations in the window of all ranks / slowest rank's
-window time. The solve then runs to completion (every instance optimal / acceptable / max_iter /
-failed), and the full solve is reported beside it (sqp_full: it/s over the whole solve,
-converged solves/s, statuses, lap times, KKT errors). Multi-GPU: one process per GPU, instances
-sharded (weak scaling), no communication while solving; per-instance 32-byte records
-{lap, KKT error, iterations, status} are all-gathered over RCCL afterwards.
+window time. Multi-GPU: one process per GPU, instances sharded (weak scaling), no communication
+while solving.
 
-Also measured: the evaluation kernel alone (ato_eval over the same batch, `evals`, with the
-k_eval HBM roofline from >= 10 sampled launches) and the CPU baselines (rank 0, N = 1).
+A plain run does only that: every instance's iteration limit is W + K, so the solve ends with the
+window (the result line's config.max_iter says so), and the result line follows.
 
-    python bench.py [--gpus N --steps K --warmup W --batch B --max-iter 1000]
+--dump-outputs DIR writes what that solve returned to its caller after the last timed step (x, f,
+lam_g, lam_x, iterations and status code per instance) as DIR/<name>.npy, float64, at most 64 MB
+in all (beyond that, a fixed seeded sample of the instances, listed in instances.npy). The inputs
+are seeded, so two builds can be compared output for output. (With --full the same arrays are those
+of the completed solve.)
+
+--full adds everything else, as one run: the solve then runs to completion under --max-iter
+(every instance optimal / acceptable / max_iter / failed) and is reported beside the window
+(sqp_full: it/s over the whole solve, converged solves/s, statuses, lap times, KKT errors); the
+per-instance 32-byte records {lap, KKT error, iterations, status} are all-gathered over RCCL
+afterwards; the first optimal instance is re-solved alone (lap-time check); the evaluation kernel
+is timed alone (ato_eval over the same batch, `evals`, with the k_eval HBM roofline from >= 10
+sampled launches); and the CPU baselines run (rank 0, N = 1).
+
+    python bench.py [--gpus N --steps K --warmup W --batch B] [--dump-outputs DIR] [--full [--max-iter 1000]]
 '''
 import argparse
 import json
@@ -47,7 +58,14 @@ def parse():
     ap.add_argument('--steps', type=int, default=20, help='timed lockstep SQP iterations (the driver runs 20)')
     ap.add_argument('--warmup', type=int, default=5, help='untimed lockstep iterations before the window (driver: 5)')
     ap.add_argument('--batch', type=int, default=512, help='instances per GPU')
-    ap.add_argument('--max-iter', type=int, default=1000, help="IPOPT's max_iter (base_raceline.py:54)")
+    ap.add_argument('--max-iter', type=int, default=1000,
+                    help="IPOPT's max_iter (base_raceline.py:54) of the --full solve; a plain run stops at "
+                         'warmup + steps')
+    ap.add_argument('--full', action='store_true',
+                    help='also: the solve to completion (sqp_full), the B = 1 re-solve, the evaluation kernel alone '
+                         '(evals, roofline) and the CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the arrays the timed solve returned as DIR/<name>.npy (float64, at most 64 MB)')
     ap.add_argument('--eval-steps', type=int, default=200)
     ap.add_argument('--eval-warmup', type=int, default=20)
     ap.add_argument('--dtype', choices=['f64', 'f32'], default='f64', help='evaluation-kernel bench dtype')
@@ -76,7 +94,7 @@ def parse():
     return ap.parse_args()
 
 
-def eval_bench(spec, W, args, dev, world):
+def eval_bench(spec, W, args, dev, world, dump=None):
     '''
     ato_eval over the batch (inputs resident in HBM): evals/s and the k_eval roofline. Kernel
     durations come from HIP events recorded inside the library on the evaluation stream, on
@@ -115,8 +133,10 @@ def eval_bench(spec, W, args, dev, world):
     k_ms, r_ms, calls = bn.problem.timing_read()
     bn.problem.timing_start(0)
     bn.problem.timing_stride(1)
-    g, _, f, _ = bn.results()
+    g, J, f, gf = bn.results()
     assert np.isfinite(g).all() and np.isfinite(f).all(), 'non-finite evaluation results'
+    if dump and int(os.environ.get('RANK', '0')) == 0:
+        dump_outputs(dump, {'g': g, 'J': J, 'f': f, 'grad_f': gf})
     elem = 8 if args.dtype == 'f64' else 4
     # read w; write g, J, the structural nonzeros of grad f (h and the inputs: the states
     # never enter the cost) and f
@@ -216,6 +236,36 @@ def cpu_baseline(W, budget_s, spec_kw):
             'sqp_all_cores_error': allc.get('error') if allc else None}
 
 
+DUMP_BYTES = 60 * 10**6    # --dump-outputs writes at most 64 MB; the rest is room for the .npy headers
+
+
+def dump_outputs(path, arrays):
+    '''
+    --dump-outputs: write the instance-major arrays (name -> [B, ...]) as path/<name>.npy in float64.
+    Beyond DUMP_BYTES in all, the same seeded sample of the instances of every array (instances.npy
+    lists their indices).
+    '''
+    arrays = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for k, v in arrays.items()}
+    B = len(next(iter(arrays.values())))
+    per_instance = sum(a.nbytes for a in arrays.values()) // max(B, 1) + 8
+    idx = np.arange(B)
+    if per_instance * B > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(B, size=max(1, DUMP_BYTES // per_instance), replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'instances.npy'), idx.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f'{k}.npy'), a[idx])
+
+
+def result_arrays(res):
+    ''' what a batched solve returned to its caller, instance-major '''
+    from aircraft_trajectory_optimization_amd.solver.batched_ipm import STATUS_NAMES
+    code = {v: k for k, v in STATUS_NAMES.items()}
+    return {'x': res.x.T.cpu().numpy(), 'f': res.f.cpu().numpy(), 'lam_g': res.lam_g.T.cpu().numpy(),
+            'lam_x': res.lam_x.T.cpu().numpy(), 'iters': np.asarray(res.iters),
+            'status': np.array([code[s] for s in res.status])}
+
+
 def main():
     args = parse()
     import torch
@@ -246,14 +296,18 @@ def main():
     B = args.batch
     track = 'racetrack' if args.track == 'race' else 'fig8'
     seeds = shard_seeds(rank, world, B)
-    W, _, _ = seeded_instances(spec, seeds)
+    # a plain run ends the solve with the timed window: the iteration limit of every instance
+    max_iter = args.max_iter if args.full else min(args.max_iter, args.warmup + args.steps)
 
-    # ---- 1. the evaluation kernel alone (k_eval roofline)
-    evals, roofline = eval_bench(spec, W, args, dev, world)
+    # ---- 1. the evaluation kernel alone (k_eval roofline): --full, or the headline of --no-solve
+    evals = roofline = W = None
+    if args.full or args.no_solve:
+        W, _, _ = seeded_instances(spec, seeds)
+        evals, roofline = eval_bench(spec, W, args, dev, world, dump=args.dump_outputs if args.no_solve else None)
 
     out = None
     if not args.no_solve:
-        # ---- 2. the batched SQP solve: lockstep iterations [W, W + K) timed, then to completion
+        # ---- 2. the batched SQP solve: lockstep iterations [W, W + K) timed, then (--full) to completion
         sync = lambda: torch.cuda.synchronize(dev)  # noqa: E731
         hook, win = window_timer(args.warmup, args.steps, sync)
         sync()
@@ -270,14 +324,14 @@ def main():
                                                         progress=args.progress, **wkw)
             sync()
             t0 = time.perf_counter()
-            solver = device_solver(spec, len(seeds), LBW, UBW, IPMOptions(max_iter=args.max_iter, tol=args.tol),
+            solver = device_solver(spec, len(seeds), LBW, UBW, IPMOptions(max_iter=max_iter, tol=args.tol),
                                    device=dev, jac32=args.jac32)
             res = solver.solve(Wws, on_iteration=hook, progress=args.progress)
         else:
             t0 = time.perf_counter()
             if args.jac32:
                 raise SystemExit('--jac32 is the config-5 solve leg: --track fig8')
-            res, solver, _ = solve_shard(spec, seeds, IPMOptions(max_iter=args.max_iter, tol=args.tol), on_iteration=hook,
+            res, solver, _ = solve_shard(spec, seeds, IPMOptions(max_iter=max_iter, tol=args.tol), on_iteration=hook,
                                          progress=args.progress)
         sync()
         t_solve = time.perf_counter() - t0
@@ -290,16 +344,22 @@ def main():
         if world > 1:
             dist.all_reduce(counts, op=dist.ReduceOp.SUM)
             dist.all_reduce(timed_min, op=dist.ReduceOp.MIN)
-        solve_s = max_over_ranks(t_solve, dev)
-        rec = solve_records(spec, res, solver)
-        allrec = gather_solve_records(rec)            # RCCL all-gather of the 32-byte records
-        # the optional audit gather of the converged decision vectors, after the window
-        sol_gather = time_solution_gathers(res.x.T.contiguous(), sync, dev) if world > 1 else None
-        lockstep = int(len(solver.history))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, result_arrays(res))
+        allrec = sol_gather = None
+        if args.full:
+            solve_s = max_over_ranks(t_solve, dev)
+            rec = solve_records(spec, res, solver)
+            allrec = gather_solve_records(rec)            # RCCL all-gather of the 32-byte records
+            # the optional audit gather of the converged decision vectors, after the window
+            sol_gather = time_solution_gathers(res.x.T.contiguous(), sync, dev) if world > 1 else None
+            lockstep = int(len(solver.history))
         if rank == 0:
-            summ = summarize_records(allrec)
             steps_timed = int(timed_min.item())
             value = float(counts[0].item()) / window_s
+            sqp_full = lap_err = None
+        if rank == 0 and args.full:
+            summ = summarize_records(allrec)
             sqp_full = {'window': {'instance_iterations': int(counts[0].item()),
                                    'main_loop': int(counts[2].item()), 'restoration_phases': int(counts[3].item()),
                                    'note': 'value counts both, as IPOPT\'s iteration counter (and max_iter, and '
@@ -312,7 +372,6 @@ def main():
                         **summ, 'solver_stats': {k: v for k, v in res.stats.items() if k not in ('resto_phases',)}}
             if sol_gather is not None:
                 sqp_full['solutions_all_gathered'] = sol_gather
-            lap_err = None
             if not args.no_single:
                 # the first OPTIMAL instance re-solved alone (B = 1) from the same start: batched vs
                 # single-instance lap time (an unconverged instance would compare two stopped iterates)
@@ -331,6 +390,7 @@ def main():
                                                   'single_lap_s': lap1, 'batched_status': res.status[i0],
                                                   'single_status': r1.status[0], 'batched_iters': int(res.iters[i0]),
                                                   'single_iters': int(r1.iters[0])}
+        if rank == 0:
             out = {
                 'metric': METRIC,
                 'value': value,
@@ -352,8 +412,9 @@ def main():
                 'config': {'workload': f'{track}_parametric_{args.pose}_drone_colloc_N50_K4_'
                                        f'{"warm" if args.track == "fig8" else "cold"}_start_batched_sqp',
                            'N': 50, 'K': 4, 'nz': spec.nz, 'nu': 4, 'batch_per_gpu': B, 'global_batch': world * B,
-                           'max_iter': args.max_iter, 'tol': args.tol, 'layout': args.layout,
-                           'parallelism': f'instances sharded x{world}, records all-gathered'},
+                           'max_iter': max_iter, 'tol': args.tol, 'layout': args.layout,
+                           'parallelism': f'instances sharded x{world}'
+                                          + (', records all-gathered' if args.full else '')},
                 'lap_time_err_vs_casadi': None,
                 'lap_time_err_note': 'CasADi/IPOPT cannot run in this pipeline (SURVEY F8): lap-time parity with it '
                                      'is unpinned; the transcription is pinned to the reference\'s own code '
@@ -366,7 +427,7 @@ def main():
                 'evals': evals,
                 'sqp_full': sqp_full,
             }
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 cb = cpu_baseline(W, args.cpu_seconds, spec_kw)
                 # a CPU cold solve needs hundreds of iterations (the GPU run's median for a converged
                 # instance), far beyond the bounded sample: converged solves/s on the host cores is the
@@ -415,7 +476,9 @@ def obstacles_main(args, dev, world, rank):
     seeds = shard_seeds(rank, world, B)
     prob = config4_problem()
     dspec = ProblemSpec(prob['line'], prob['cfg'].copy(), prob['dveh'], 'parametric', sphere_table=prob['table'])
-    evals, roofline = eval_bench(dspec, np.repeat(dspec.w0[None], B, axis=0), args, dev, world)
+    evals = roofline = None
+    if args.full:
+        evals, roofline = eval_bench(dspec, np.repeat(dspec.w0[None], B, axis=0), args, dev, world)
     sync = lambda: torch.cuda.synchronize(dev)  # noqa: E731
     hook, win = window_timer(args.warmup, args.steps, sync)
     sync()
@@ -433,6 +496,8 @@ def obstacles_main(args, dev, world, rank):
         dist.all_reduce(counts, op=dist.ReduceOp.SUM)
     st = r['status']
     ok = np.array([x in ('optimal', 'acceptable') for x in st])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'lap': r['lap'], 'iters': r['iters'], 'converged': ok})
     if rank == 0:
         steps_timed = int(win['timed'])
         out = {'metric': METRIC, 'value': float(counts[0].item()) / window_s,

@@ -53,16 +53,16 @@ for s in $STEPS; do
                for t in 1e2 1e4; do
                    ATO_KKT_SADDLE=1 ATO_KKT_SADDLE_TAU=$t run c3_sad_tau$t 600 python -u tools/solver_ab.py --what config3 --tag "saddle tau $t" --out "$OUT/c3_sad_tau$t.json"
                done ;;
-        bench5solve) run bench5_dcm_solve 1100 python -u bench.py --track fig8 --pose dcm --batch ${B5:-8192} --max-iter ${B5_MAXIT:-150} --no-cpu-baseline --progress 20 ;;
+        bench5solve) run bench5_dcm_solve 1100 python -u bench.py --full --track fig8 --pose dcm --batch ${B5:-8192} --max-iter ${B5_MAXIT:-150} --no-cpu-baseline --progress 20 ;;
         jtyab) run pytest_jty 200 python -u -m pytest tests/test_gpu_ipm_kernels.py -x -v --timeout 120 --timeout-method thread -p no:cacheprovider -k js_jty
                for v in 0 1; do
                    ATO_IPM_FUSED_JTY=$v run solve_jty$v 600 python tools/solve_batched.py --batch 512 --max-iter 1000 --cold --no-host --out "$OUT/solve_jty$v.json"
                done ;;
-        bench5j32) run bench5_dcm_jac32 1100 python -u bench.py --track fig8 --pose dcm --batch ${B5:-8192} --max-iter ${B5_MAXIT:-150} --jac32 --tol 1e-6 --no-cpu-baseline --progress 20 ;;
-        bench4) run bench4_obstacles 900 python bench.py --track obstacles --batch 512 --no-cpu-baseline ;;
+        bench5j32) run bench5_dcm_jac32 1100 python -u bench.py --full --track fig8 --pose dcm --batch ${B5:-8192} --max-iter ${B5_MAXIT:-150} --jac32 --tol 1e-6 --no-cpu-baseline --progress 20 ;;
+        bench4) run bench4_obstacles 900 python bench.py --full --track obstacles --batch 512 --no-cpu-baseline ;;
         abnew) run ab_new 900 python -u tools/solver_ab.py --what ${AB_WHAT:-fig8,config3} --tag new --out "$OUT/ab_new.json" ;;
         smoke) run smoke 300 python -c 'import __graft_entry__ as g; g.smoke()' ;;
-        bench) run bench 900 python bench.py ;;
+        bench) run bench 900 python bench.py --full ;;
         bench32) run bench_f32 300 python bench.py --steps 50 --warmup 10 --dtype f32 --no-cpu-baseline --no-solve ;;
         benchim) run bench_im 300 python bench.py --steps 50 --warmup 10 --layout instance --no-cpu-baseline --no-solve ;;
         benchbig) run bench_b4096 300 python bench.py --steps 20 --warmup 5 --batch 4096 --no-cpu-baseline --no-solve ;;

@@ -54,6 +54,8 @@ static void release(ato_handle* h) {
     (void)hipFree(h->d_amask);
     (void)hipFree(h->d_dJ);
     (void)hipFree(h->d_dgf);
+    (void)hipFree(h->d_lift);
+    (void)hipFree(h->d_replay_w);
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
     h->events.clear();
 }
@@ -124,6 +126,13 @@ static int create_impl(const ato_problem_desc* desc, ato_handle** out) {
         release(h);
         delete h;
         return rc;
+    }
+    // the replay's weight table, sized for the largest substep count: ato_replay itself allocates nothing
+    if (hipMalloc((void**)&h->d_replay_w, (size_t)(2 * ato::REPLAY_SMAX + 1) * (ATO_KMAX + 1) * sizeof(double)) !=
+        hipSuccess) {
+        release(h);
+        delete h;
+        return fail(ATO_ERR_HIP, "replay weight table: out of device memory");
     }
     h->pd = h->L.p;
     h->pd.geom = h->d_geom;
@@ -409,6 +418,44 @@ extern "C" int ato_hess_eval(ato_handle* h, int32_t batch, int32_t layout, const
     });
     if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("hessian launch: ") + hipGetErrorString(e));
     return ATO_OK;
+}
+
+extern "C" int ato_replay_set_lift(ato_handle* h, const double* lift) {
+    if (!h || !lift) return fail(ATO_ERR_ARG, "null argument");
+    if (h->L.p.frame == ato::GLOBAL) return ATO_OK;      // not needed: ignored
+    const size_t bytes = (size_t)(h->L.p.N + 1) * ato::REPLAY_LIFT_W * sizeof(double);
+    if (!h->d_lift) ATO_HIP(hipMalloc((void**)&h->d_lift, bytes));
+    ATO_HIP(hipMemcpy(h->d_lift, lift, bytes, hipMemcpyHostToDevice));
+    return ATO_OK;
+}
+
+static int replay_impl(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t substeps,
+                       double* zsim, double* err, double* traj, void* stream) {
+    if (!h) return fail(ATO_ERR_ARG, "null handle");
+    const ato::ProbD& p = h->pd;
+    const char* msg = "";
+    if (int rc = ato::replay_check(p, h->d_lift != nullptr, batch, layout, substeps, &msg)) return fail(rc, msg);
+    if (!w || !zsim || !err) return fail(ATO_ERR_ARG, "null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    if (h->replay_S != substeps) {
+        std::vector<double>& tab = h->replay_w_host[substeps];
+        if (tab.empty()) {
+            tab.resize((size_t)(2 * substeps + 1) * p.K1);
+            ato::replay_weights(p.tau, p.K1, substeps, tab.data());
+        }
+        ATO_HIP(hipMemcpyAsync(h->d_replay_w, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        h->replay_S = substeps;
+    }
+    const ato::ReplayD r{substeps, traj ? 1 : 0, h->d_replay_w, p.frame == ato::GLOBAL ? nullptr : h->d_lift};
+    hipError_t e = hipSuccess;
+    ato::with_model(p, [&]<class M>() { e = ato::launch_replay<M>(p, r, batch, layout, w, zsim, err, traj, st); });
+    if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("replay launch: ") + hipGetErrorString(e));
+    return ATO_OK;
+}
+
+extern "C" int ato_replay(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t substeps,
+                          double* zsim, double* err, double* traj, void* stream) {
+    ATO_NOEXCEPT_BODY(replay_impl(h, batch, layout, w, substeps, zsim, err, traj, stream))
 }
 
 extern "C" int ato_eval(ato_handle* h, int32_t batch, int32_t layout, const double* w, double* g,

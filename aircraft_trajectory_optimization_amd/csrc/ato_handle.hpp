@@ -1,8 +1,10 @@
 // ato_handle.hpp -- the opaque ato_handle of include/ato.h (library-internal).
 #pragma once
+#include <map>
 #include <vector>
 #include <hip/hip_runtime.h>
 #include "ato_kernels.hpp"
+#include "ato_replay.hpp"
 
 struct ato_handle {
     ato::Layout L;
@@ -46,4 +48,11 @@ struct ato_handle {
     double* d_dgf = nullptr;
     int32_t hess_reserved = 0;
     int32_t hess_colors = 0;
+    // replay (ato_replay.hpp): lift table [N+1][12] (parametric problems), the Lagrange weight table of
+    // the substep count last used (sized for REPLAY_SMAX) and the host tables it is uploaded from, one
+    // per substep count and never rewritten (an upload may still be queued on a stream)
+    double* d_lift = nullptr;
+    double* d_replay_w = nullptr;
+    int32_t replay_S = 0;
+    std::map<int32_t, std::vector<double>> replay_w_host;
 };

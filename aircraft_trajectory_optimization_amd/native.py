@@ -19,6 +19,7 @@ ATO_FRAME_GLOBAL, ATO_FRAME_PARAMETRIC = 0, 1
 ATO_TRANS_COLLOCATION, ATO_TRANS_RK4 = 0, 1
 ATO_GATE_CIRCLE, ATO_GATE_SQUARE = 0, 1
 ATO_LAYOUT_INTERLEAVED, ATO_LAYOUT_INSTANCE_MAJOR = 0, 1
+ATO_OK, ATO_ERR_ARG, ATO_ERR_UNSUPPORTED, ATO_ERR_HIP, ATO_ERR_STATE = 0, -1, -2, -3, -4
 ABI_VERSION = 3
 CPC_MAX = 16                 # ATO_CPC_MAX
 
@@ -113,7 +114,8 @@ EXPORTED_SYMBOLS = ('ato_create', 'ato_destroy', 'ato_sizes', 'ato_sparsity', 'a
                     'ato_timing', 'ato_timing_read', 'ato_timing_stride', 'ato_last_error', 'ato_version',
                     'ato_kkt_create', 'ato_kkt_destroy', 'ato_kkt_reserve', 'ato_kkt_factor', 'ato_kkt_solve',
                     'ato_kkt_residual', 'ato_kkt_residual_list', 'ato_set_instance_spheres',
-                    'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity') + IPM_SYMBOLS
+                    'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity', 'ato_replay_set_lift',
+                    'ato_replay') + IPM_SYMBOLS
 
 
 def library_path() -> str:
@@ -149,6 +151,8 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
         lib.ato_sphere_rows.argtypes = [vp, i32p]
         lib.ato_gradf_mode.argtypes = [vp, ctypes.c_int32]
         lib.ato_gradf_sparsity.argtypes = [vp, i32p, i32p]
+        lib.ato_replay_set_lift.argtypes = [vp, vp]
+        lib.ato_replay.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, vp, vp]
         lib.ato_kkt_create.argtypes = [vp, ctypes.POINTER(vp)]
         lib.ato_kkt_destroy.argtypes = [vp]
         lib.ato_kkt_reserve.argtypes = [vp, ctypes.c_int32]
@@ -185,7 +189,8 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
         for fn in ('ato_create', 'ato_destroy', 'ato_sizes', 'ato_sparsity', 'ato_bounds', 'ato_reserve',
                    'ato_eval', 'ato_eval_f32', 'ato_hess_sparsity', 'ato_hess_eval', 'ato_timing',
                    'ato_timing_read', 'ato_timing_stride', 'ato_mesh_create', 'ato_mesh_destroy', 'ato_mesh_signed_distance',
-                   'ato_set_instance_spheres', 'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity'):
+                   'ato_set_instance_spheres', 'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity',
+                   'ato_replay_set_lift', 'ato_replay'):
             getattr(lib, fn).restype = ctypes.c_int
     return lib
 
@@ -385,6 +390,32 @@ class NativeProblem:
         ''' Hessian of the Lagrangian on device pointers (fp64, asynchronous on `stream`) '''
         self._check(self.lib.ato_hess_eval(self.handle, int(batch), int(layout), w, lam, sigma, hess,
                                            stream or None))
+
+    def replay_set_lift(self, table: np.ndarray):
+        ''' lift table of a parametric problem: host (N + 1, 12) array (ProblemSpec.lift_table), copied '''
+        t = np.ascontiguousarray(table, dtype=np.float64)
+        if t.shape != (int(self.holder.desc.N) + 1, 12):
+            raise ValueError(f'lift table must be (N + 1, 12), got {t.shape}')
+        self._check(self.lib.ato_replay_set_lift(self.handle, t.ctypes.data))
+
+    def replay_rc(self, batch: int, w: int, substeps: int, zsim: int, err: int, traj: int = 0,
+                  layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0) -> int:
+        ''' ato_replay on device pointers; returns the library's code (ato_last_error has the message) '''
+        return self.lib.ato_replay(self.handle, int(batch), int(layout), w or None, int(substeps), zsim or None,
+                                   err or None, traj or None, stream or None)
+
+    def replay_ptrs(self, batch: int, w: int, substeps: int, zsim: int, err: int, traj: int = 0,
+                    layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0):
+        '''
+        Replay the decision vectors w through the vehicle ODE (asynchronous on `stream`): zsim
+        [N nz x batch], err [N 4 x batch], traj [N substeps nz x batch] or 0. Problems the replay does
+        not cover (RK4 transcription, relative attitude) raise NotImplementedError with the library's
+        message.
+        '''
+        rc = self.replay_rc(batch, w, substeps, zsim, err, traj, layout, stream)
+        if rc == ATO_ERR_UNSUPPORTED:
+            raise NotImplementedError(self.lib.ato_last_error().decode())
+        self._check(rc)
 
     def timing_start(self, max_calls: int):
         ''' record HIP events around the kernels of the next max_calls evaluations '''

@@ -126,6 +126,43 @@ class BatchedNLP:
                                     self.hess.data_ptr(), layout=self.layout, stream=st.cuda_stream)
         return self.hess
 
+    def replay(self, W=None, substeps: int = 16, trajectory: bool = False, stream=None):
+        '''
+        Replay decision vectors through the vehicle ODE (ato_replay, asynchronous on `stream`): per
+        interval the start state, lifted to the global model, is integrated over h_n with `substeps`
+        RK4 steps under the solution's own inputs and compared with the collocation polynomial's end
+        value. W: fp64 device tensor in this batch's layout ((nw, B) interleaved, (B, nw) instance-
+        major) or a host array (B, nw); None: the resident w. Returns (zsim, err, traj) in the layout:
+        interleaved (N, nz, B), (N, 4, B), (N, substeps, nz, B); instance-major (B, N, nz), (B, N, 4),
+        (B, N, substeps, nz); traj is None unless `trajectory`. err rows: position (m), attitude (rad),
+        velocity (m/s), body rate (rad/s). Problems the replay does not cover raise NotImplementedError.
+        '''
+        sp_, B = self.spec, self.batch
+        il = self.layout == native.ATO_LAYOUT_INTERLEAVED
+        if W is None:
+            if self.w is None or self.fp32:
+                raise TypeError('replay needs fp64 decision vectors (pass W)')
+            W = self.w
+        elif not torch.is_tensor(W):
+            t = torch.as_tensor(np.array(W, np.float64).reshape(B, -1))
+            W = (t.T.contiguous() if il else t.contiguous()).to(self.device)
+        if W.dtype != torch.float64 or tuple(W.shape) != ((self.problem.nw, B) if il else (B, self.problem.nw)):
+            raise ValueError('W must be fp64 in the layout of this batch')
+        W = W.contiguous()
+        if sp_.param and not getattr(self, '_replay_lift', False) and not sp_.rk4 and sp_.vehicle.global_r:
+            self.problem.replay_set_lift(sp_.lift_table())
+            self._replay_lift = True
+        S = int(substeps)
+        opts = {'device': self.device, 'dtype': torch.float64}
+        shape = (lambda *d: (*d, B)) if il else (lambda *d: (B, *d))
+        zsim = torch.empty(shape(sp_.N, sp_.nz), **opts)
+        err = torch.empty(shape(sp_.N, 4), **opts)
+        traj = torch.empty(shape(sp_.N, max(S, 1), sp_.nz), **opts) if trajectory else None
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self.problem.replay_ptrs(B, W.data_ptr(), S, zsim.data_ptr(), err.data_ptr(),
+                                 traj.data_ptr() if trajectory else 0, layout=self.layout, stream=st.cuda_stream)
+        return zsim, err, traj
+
     def _host(self, t: torch.Tensor) -> np.ndarray:
         a = t.detach().to('cpu', torch.float64).numpy()
         return a.T.copy() if self.layout == native.ATO_LAYOUT_INTERLEAVED else a

@@ -331,6 +331,22 @@ class ProblemSpec:
         en2 = self.line.p2en(self.line.s_max() - 0.001)
         return np.array([[ey1 @ ey2, en1 @ ey2], [ey1 @ en2, en1 @ en2]]).reshape(-1)
 
+    def lift_table(self) -> np.ndarray:
+        '''
+        Replay lift table (ato_replay_set_lift): (N + 1, 12) rows [x_c (3), Rp (9, row-major columns
+        e_s e_y e_n: the layout of node_geom)] at the interval boundaries interval_s[0..N], the last one
+        s_max itself. A parametric state (s_n, y, n, ...) has the global position x_c + y e_y + n e_n,
+        the same centreline terms the gate rows place a gate with (_gates: p2xc / p2ey / p2en).
+        '''
+        if not self.param:
+            raise ValueError('the lift table belongs to parametric problems')
+        s = np.asarray(self.interval_s, float)
+        xc, es, ey, en = self.line.p2xc(s), self.line.p2es(s), self.line.p2ey(s), self.line.p2en(s)
+        tbl = np.zeros((self.N + 1, 12))
+        tbl[:, :3] = xc.T
+        tbl[:, 3:] = np.stack([es, ey, en], axis=2).transpose(1, 0, 2).reshape(-1, 9)
+        return tbl
+
     def native_spec(self) -> dict:
         ''' dict consumed by native.DescHolder '''
         v = self.vehicle

@@ -56,6 +56,7 @@ class _Raceline:
 
     # evaluator over libato.so (tests substitute the CPU build of the programs here)
     evaluator_factory = None
+    _last_solution = None
 
     def __init__(self, line: BaseCenterline, config: RacelineConfig, vehicle_config, ws_raceline=None,
                  ws_model=None, guess=None):
@@ -93,6 +94,7 @@ class _Raceline:
         self.ipopt_time = self.solve_time - self.feval_time
         out = self._unpack(x, success)
         _SOLUTIONS[id(out)] = (self.spec, x.copy(), out)
+        self._last_solution = id(out)
         return out
 
     def _solve_device(self, opts):
@@ -122,6 +124,25 @@ class _Raceline:
         self.solve_time = time.time() - t0
         self.feval_time = ev.feval_time
         return self.result.x, self.result.success
+
+    def replay(self, results_or_x=None, substeps: int = 16):
+        '''
+        Replay a solution of this problem through the vehicle dynamics on the device
+        (raceline/replay.py): `results_or_x` is a RacelineResults of solve() (default: the last one)
+        or a decision vector. Returns the ReplayResult of that one instance. Solver classes the
+        replay does not cover (RK4 transcription, relative attitude) raise NotImplementedError.
+        '''
+        from aircraft_trajectory_optimization_amd.raceline.replay import replay_solutions
+        if results_or_x is None or isinstance(results_or_x, RacelineResults):
+            key = id(results_or_x) if results_or_x is not None else self._last_solution
+            if key not in _SOLUTIONS:
+                raise ValueError('no decision vector is recorded for these results (call solve() first)')
+            x = _SOLUTIONS[key][1]
+        else:
+            x = np.asarray(results_or_x, float).reshape(-1)
+        if x.shape[0] != self.spec.nw:
+            raise ValueError(f'decision vector of length {x.shape[0]}, problem has {self.spec.nw}')
+        return replay_solutions(self.spec, x[None], substeps=substeps)
 
     def get_ws(self) -> RacelineResults:
         ''' the initial guess, unpacked like a solution (base_raceline.py:193-198) '''

@@ -195,6 +195,29 @@ int ato_mesh_destroy(ato_mesh* mesh);
 int ato_mesh_signed_distance(ato_mesh* mesh, int32_t n, const double* points, double* dist, double* closest,
                              void* stream);
 
+/* Replay of collocation solutions through the vehicle ODE (csrc/ato_replay.hpp): per (instance,
+ * interval) the start state Z[n,0], lifted to the global model, is integrated over h_n with
+ * `substeps` classical RK4 steps under the solution's own inputs u(tau) = sum_j l_j(tau) U[n,j] and
+ * compared with the collocation polynomial's end value sum_k D_k Z[n,k]. The dynamics are the global
+ * variant of the problem's model; nothing renormalises the attitude on the way. It certifies the
+ * dynamics of w, not optimality or constraints. Collocation problems in the global frame or
+ * parametric with global_r; the RK4 transcription and the relative attitude return
+ * ATO_ERR_UNSUPPORTED.
+ *
+ * Lift table for parametric problems: host [N+1][12] = xc(3), Rp(9, layout of node_geom) at interval_s[0..N];
+ * copied. Not needed (ignored) for global-frame problems. */
+int ato_replay_set_lift(ato_handle* h, const double* lift);
+/* zsim [N*NZ x batch], err [N*4 x batch], traj [N*S*NZ x batch] or NULL; substeps in [1, 64].
+ * zsim: simulated global-model state at the end of every interval; err per interval: position error
+ * (m), attitude error (rotation angle of R(r_sim)^T R(r_ref), rad; 0 for the point mass), body /
+ * global velocity error (m/s), body-rate error (rad/s; 0 for the point mass); traj: the state after
+ * every substep. Element e of instance b at [e * batch + b] (interleaved) or [b * n + e].
+ * Asynchronous on stream; no device-wide synchronisation; the weight table is uploaded on the
+ * stream when substeps changes (calls with different substeps on different streams are the caller's
+ * to order). A parametric problem without a lift table returns ATO_ERR_STATE. */
+int ato_replay(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t substeps,
+               double* zsim, double* err, double* traj, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the evaluation stream. ato_timing(h, n)
  * allocates n event slots and starts recording (n = 0 stops); while on, each ato_eval
  * records events around its Jacobian kernel and its cost-reduction kernel. ato_timing_read

@@ -1112,6 +1112,238 @@ __global__ __launch_bounds__(256) void k_resto_rows(int m, int W, int rows, cons
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The restoration phase's nested solve (batched_ipm.py _RestorationEvaluator, _RestorationKKT and the
+// KKT residual of a backend without one): the wrappers' gathers, scatters and elementwise algebra as
+// column kernels, one wave per row x 64 instance columns like k_js_jty. Every product, quotient and sum
+// is rounded on its own in the order of the torch formulation (no contraction), and every segment sum
+// starts from 0 and adds its entries in the structure's order, as torch's segment_reduce does: the
+// results are bit for bit the torch ones.
+// ------------------------------------------------------------------------------------------
+constexpr int RROWS = 16;     // rows per workgroup of the elementwise restoration kernels (4 per wave)
+constexpr int GRID_Y_MAX = 65535;
+
+// out = rhs - K v, K = [[H + diag(dx), Js^T], [Js, diag(dr)]] (batched_ipm.py rhs - _Kmul(H, Js, dx, dr, v)):
+// row i < n: (dx v_i + sum_jt Js v_y) + sum_w H v_x; row n + r: sum_j Js v_x + dr v_y
+__global__ __launch_bounds__(256) void k_kmul_residual(
+    int n, int m, int W, const int32_t* __restrict__ jt_ptr, const int32_t* __restrict__ jt_src,
+    const int32_t* __restrict__ jt_row, const int32_t* __restrict__ j_ptr, const int32_t* __restrict__ jc,
+    const int32_t* __restrict__ w_ptr, const int32_t* __restrict__ w_src, const int32_t* __restrict__ w_col,
+    const double* __restrict__ H, const double* __restrict__ Js, const double* __restrict__ dx,
+    const double* __restrict__ dr, const double* __restrict__ v, const double* __restrict__ rhs,
+    double* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int i = blockIdx.y * 4 + (threadIdx.x >> 6);          // one wave per row: uniform entry loops
+    if (i >= n + m || b >= W) return;
+    const long long o = (long long)i * W + b;
+    double acc;
+    if (i < n) {
+        acc = dx[o] * v[o];
+        double t = 0.0;
+        for (int k = jt_ptr[i], k1 = jt_ptr[i + 1]; k < k1; ++k) {
+            const double p = Js[(long long)jt_src[k] * W + b] * v[(long long)(n + jt_row[k]) * W + b];
+            t = t + p;
+        }
+        acc = acc + t;
+        if (H) {
+            double u = 0.0;
+            for (int k = w_ptr[i], k1 = w_ptr[i + 1]; k < k1; ++k) {
+                const double p = H[(long long)w_src[k] * W + b] * v[(long long)w_col[k] * W + b];
+                u = u + p;
+            }
+            acc = acc + u;
+        }
+    } else {
+        const int r = i - n;
+        double s = 0.0;
+        for (int e = j_ptr[r], e1 = j_ptr[r + 1]; e < e1; ++e) {
+            const double p = Js[(long long)e * W + b] * v[(long long)jc[e] * W + b];
+            s = s + p;
+        }
+        const double q = dr[(long long)r * W + b] * v[o];
+        acc = s + q;
+    }
+    out[o] = rhs[o] - acc;
+}
+
+// the restoration NLP at X = (x, p, nn): gr = (sg g - p) + nn; unless trial: gfr = [(zeta dr2)(x - x_ref);
+// rho] and the expanded Jacobian jr (row r: its original entries jv sg_r at pos_orig, then -1, +1 at pe)
+__global__ __launch_bounds__(256) void k_resto_eval(
+    int n0, int m, int W, int trial, const int32_t* __restrict__ j_ptr, const int32_t* __restrict__ pos_orig,
+    const int32_t* __restrict__ pe, const double* __restrict__ X, const double* __restrict__ g,
+    const double* __restrict__ jv, const double* __restrict__ sg, const double* __restrict__ x_ref,
+    const double* __restrict__ dr2, const double* __restrict__ zeta, double rho, double* __restrict__ gr,
+    double* __restrict__ gfr, double* __restrict__ jr) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (b >= W) return;
+    if (i < m) {
+        const long long o = (long long)i * W + b;
+        const double s = sg[o];
+        const double t = s * g[o];
+        const double u = t - X[(long long)(n0 + i) * W + b];
+        gr[o] = u + X[(long long)(n0 + m + i) * W + b];
+        if (!trial) {
+            for (int e = j_ptr[i], e1 = j_ptr[i + 1]; e < e1; ++e)
+                jr[(long long)pos_orig[e] * W + b] = jv[(long long)e * W + b] * s;
+            const long long q = (long long)pe[i] * W + b;
+            jr[q] = -1.0;
+            jr[q + W] = 1.0;
+        }
+    }
+    if (!trial && i < n0 + 2 * m) {
+        const long long o = (long long)i * W + b;
+        double v = rho;
+        if (i < n0) {
+            const double a = zeta[b] * dr2[o];
+            const double d = X[o] - x_ref[o];
+            v = a * d;
+        }
+        gfr[o] = v;
+    }
+}
+
+// the restoration NLP's Hessian on its expanded pattern: h[k] = H0[src[k]] (0 where the base pattern has
+// no entry, src < 0), plus (sigma zeta) dr2_i on the diagonal entry of x_i (dcol[k] = i, else -1)
+__global__ __launch_bounds__(256) void k_resto_hess(
+    int nnz, int W, const int32_t* __restrict__ src, const int32_t* __restrict__ dcol,
+    const double* __restrict__ H0, const double* __restrict__ sigma, const double* __restrict__ zeta,
+    const double* __restrict__ dr2, double* __restrict__ h) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * 64 + (threadIdx.x & 63);
+    if (b >= W) return;
+    const int k0 = blockIdx.y * RROWS, k1 = min(nnz, k0 + RROWS);
+    const double sz = sigma[b] * zeta[b];
+    for (int k = k0 + (threadIdx.x >> 6); k < k1; k += 4) {
+        const int s = src[k], i = dcol[k];
+        double v = s >= 0 ? H0[(long long)s * W + b] : 0.0;
+        if (i >= 0) {
+            const double a = sz * dr2[(long long)i * W + b];
+            v = v + a;
+        }
+        h[(long long)k * W + b] = v;
+    }
+}
+
+// what _RestorationKKT.factor hands to the base factorisation from (H, J): Hb = H[h_map], Jb = J[pos_orig],
+// hd = diag_new ? H[h_diag] : 0 -- rows [0, nh) Hb, [nh, nh + nj) Jb, [nh + nj, nh + nj + n0) hd (nh = 0, n0 = 0
+// without H)
+__global__ __launch_bounds__(256) void k_resto_kkt_pack(
+    int nh, int nj, int n0, int W, const int32_t* __restrict__ h_map, const int32_t* __restrict__ pos_orig,
+    const int32_t* __restrict__ h_diag, const uint8_t* __restrict__ diag_new, const double* __restrict__ H,
+    const double* __restrict__ J, double* __restrict__ Hb, double* __restrict__ Jb, double* __restrict__ hd) {
+    const int b = blockIdx.x * 64 + (threadIdx.x & 63);
+    if (b >= W) return;
+    const int total = nh + nj + n0;
+    const int k0 = blockIdx.y * RROWS, k1 = min(total, k0 + RROWS);
+    for (int k = k0 + (threadIdx.x >> 6); k < k1; k += 4) {
+        if (k < nh) {
+            Hb[(long long)k * W + b] = H[(long long)h_map[k] * W + b];
+        } else if (k < nh + nj) {
+            const int e = k - nh;
+            Jb[(long long)e * W + b] = J[(long long)pos_orig[e] * W + b];
+        } else {
+            const int i = k - nh - nj;
+            hd[(long long)i * W + b] = diag_new[i] ? H[(long long)h_diag[i] * W + b] : 0.0;
+        }
+    }
+}
+
+// one inertia-correction pass of _RestorationKKT.factor on dx = (dx_x [n0], dp [m], dn [m]): dxb = dx_x + hd
+// (hd NULL: not written), drow = (dr - 1/dp) - 1/dn and the signs of dp, dn per column (k_resto_rows), and the
+// stored dp, dn of the columns of mask replaced by the new ones. Workgroups [0, nbm) take 256 rows of m each,
+// the ones after them RROWS rows of dxb.
+__global__ __launch_bounds__(256) void k_resto_kkt_diag(
+    int n0, int m, int W, int nbm, const double* __restrict__ dx, const double* __restrict__ dr,
+    const double* __restrict__ hd, const uint8_t* __restrict__ mask, double* __restrict__ dxb,
+    double* __restrict__ drow, double* __restrict__ dps, double* __restrict__ dns, int* __restrict__ cnt) {
+#pragma clang fp contract(off)
+    __shared__ int sp[4][64], sn[4][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int col = blockIdx.x * 64 + lane;
+    if ((int)blockIdx.y >= nbm) {                               // uniform per workgroup
+        if (col >= W) return;
+        const int r0 = ((int)blockIdx.y - nbm) * RROWS, r1 = min(n0, r0 + RROWS);
+        for (int r = r0 + wv; r < r1; r += 4) {
+            const long long i = (long long)r * W + col;
+            dxb[i] = dx[i] + hd[i];
+        }
+        return;
+    }
+    const int r0 = blockIdx.y * 256, r1 = min(m, r0 + 256);
+    int np = 0, nn = 0;
+    if (col < W) {
+        const bool listed = mask[col] != 0;
+        for (int r = r0 + wv; r < r1; r += 4) {
+            const long long i = (long long)r * W + col;
+            const double a = dx[(long long)(n0 + r) * W + col], c = dx[(long long)(n0 + m + r) * W + col];
+            drow[i] = (dr[i] - 1.0 / a) - 1.0 / c;
+            np += (a > 0.0) + (c > 0.0);
+            nn += (a < 0.0) + (c < 0.0);
+            if (listed) {
+                dps[i] = a;
+                dns[i] = c;
+            }
+        }
+    }
+    sp[wv][lane] = np;
+    sn[wv][lane] = nn;
+    __syncthreads();
+    if (wv == 0 && col < W) {
+        const int tp = sp[0][lane] + sp[1][lane] + sp[2][lane] + sp[3][lane];
+        const int tn = sn[0][lane] + sn[1][lane] + sn[2][lane] + sn[3][lane];
+        if (tp) atomicAdd(&cnt[2 * col + 0], tp);
+        if (tn) atomicAdd(&cnt[2 * col + 1], tn);
+    }
+}
+
+// the reduced right-hand side of _RestorationKKT.solve: xb = [rx; (ry + rp/dp) - rn/dn] of x = (rx, rp, rn, ry)
+__global__ __launch_bounds__(256) void k_resto_kkt_rhs(int n0, int m, int W, const double* __restrict__ x,
+                                                       const double* __restrict__ dp, const double* __restrict__ dn,
+                                                       double* __restrict__ xb) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * 64 + (threadIdx.x & 63);
+    if (b >= W) return;
+    const int k0 = blockIdx.y * RROWS, k1 = min(n0 + m, k0 + RROWS);
+    for (int k = k0 + (threadIdx.x >> 6); k < k1; k += 4) {
+        const long long o = (long long)k * W + b;
+        if (k < n0) {
+            xb[o] = x[o];
+        } else {
+            const long long d = (long long)(k - n0) * W + b;
+            const double rp = x[o], rn = x[o + (long long)m * W], ry = x[o + 2LL * m * W];
+            const double t = ry + rp / dp[d];
+            xb[o] = t - rn / dn[d];
+        }
+    }
+}
+
+// after the base solve, on the columns of mask: x = [xb_x; (rp + y)/dp; (rn - y)/dn; y], y = xb[n0:]; the other
+// columns of x stay as they are
+__global__ __launch_bounds__(256) void k_resto_kkt_expand(int n0, int m, int W, const double* __restrict__ xb,
+                                                          const double* __restrict__ dp,
+                                                          const double* __restrict__ dn,
+                                                          const uint8_t* __restrict__ mask, double* __restrict__ x) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * 64 + (threadIdx.x & 63);
+    if (b >= W || !mask[b]) return;
+    const int k0 = blockIdx.y * RROWS, k1 = min(n0 + m, k0 + RROWS);
+    for (int k = k0 + (threadIdx.x >> 6); k < k1; k += 4) {
+        const long long o = (long long)k * W + b;
+        if (k < n0) {
+            x[o] = xb[o];
+        } else {
+            const long long d = (long long)(k - n0) * W + b;
+            const double y = xb[o], rp = x[o], rn = x[o + (long long)m * W];
+            x[o] = (rp + y) / dp[d];
+            x[o + (long long)m * W] = (rn - y) / dn[d];
+            x[o + 2LL * m * W] = y;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1346,6 +1578,108 @@ int ato_ipm_js_jty(int32_t n, int32_t nnz, int32_t W, const int32_t* col_ptr, co
     hipLaunchKernelGGL(k_js_jty, dim3((W + 63) / 64, (n + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream),
                        n, W, col_ptr, src, row, jv, sg, y, js, jty);
     return check_launch("ato_ipm_js_jty");
+}
+
+int ato_ipm_kmul_residual(int32_t n, int32_t m, int32_t nnz_j, int32_t nnz_w, int32_t W, const int32_t* jt_ptr,
+                          const int32_t* jt_src, const int32_t* jt_row, const int32_t* j_ptr, const int32_t* jc,
+                          const int32_t* w_ptr, const int32_t* w_src, const int32_t* w_col, const double* H,
+                          const double* Js, const double* dx, const double* dr, const double* v, const double* rhs,
+                          double* out, void* stream) {
+    if (n < 0 || m < 0 || nnz_j < 0 || nnz_w < 0 || W < 0 || (long long)n + m > 0x7fffffffLL)
+        return fail(ATO_ERR_ARG, "ato_ipm_kmul_residual: arguments");
+    if (n + m == 0 || W == 0) return 0;
+    if ((n + m + 3) / 4 > GRID_Y_MAX) return fail(ATO_ERR_ARG, "ato_ipm_kmul_residual: too many rows");
+    if (!jt_ptr || !j_ptr || !v || !rhs || !out || (n && !dx) || (m && !dr) ||
+        (nnz_j && (!jt_src || !jt_row || !jc || !Js)) || (H && (!w_ptr || (nnz_w && (!w_src || !w_col)))))
+        return fail(ATO_ERR_ARG, "ato_ipm_kmul_residual: arguments");
+    hipLaunchKernelGGL(k_kmul_residual, dim3((W + 63) / 64, (n + m + 3) / 4), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), n, m, W, jt_ptr, jt_src, jt_row, j_ptr, jc, w_ptr, w_src,
+                       w_col, H, Js, dx, dr, v, rhs, out);
+    return check_launch("ato_ipm_kmul_residual");
+}
+
+int ato_ipm_resto_eval(int32_t n0, int32_t m, int32_t nnz_j, int32_t W, int32_t trial, const int32_t* j_ptr,
+                       const int32_t* pos_orig, const int32_t* pe, const double* X, const double* g,
+                       const double* jv, const double* sg, const double* x_ref, const double* dr2,
+                       const double* zeta, double rho, double* gr, double* gfr, double* jr, void* stream) {
+    if (n0 < 0 || m < 0 || nnz_j < 0 || W < 0) return fail(ATO_ERR_ARG, "ato_ipm_resto_eval: arguments");
+    if (W == 0 || (n0 + m == 0)) return 0;
+    if ((m && (!X || !g || !sg || !gr)) ||
+        (!trial && (!X || !gfr || (n0 && (!x_ref || !dr2 || !zeta)) ||
+                    (m && (!j_ptr || !pe || !jr)) || (nnz_j && (!pos_orig || !jv)))))
+        return fail(ATO_ERR_ARG, "ato_ipm_resto_eval: arguments");
+    const int rows = trial ? m : n0 + 2 * m;
+    if (rows == 0) return 0;
+    if ((rows + 3) / 4 > GRID_Y_MAX) return fail(ATO_ERR_ARG, "ato_ipm_resto_eval: too many rows");
+    hipLaunchKernelGGL(k_resto_eval, dim3((W + 63) / 64, (rows + 3) / 4), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), n0, m, W, trial ? 1 : 0, j_ptr, pos_orig, pe, X, g, jv, sg,
+                       x_ref, dr2, zeta, rho, gr, gfr, jr);
+    return check_launch("ato_ipm_resto_eval");
+}
+
+int ato_ipm_resto_hess(int32_t nnz, int32_t W, const int32_t* src, const int32_t* dcol, const double* H0,
+                       const double* sigma, const double* zeta, const double* dr2, double* h, void* stream) {
+    if (nnz < 0 || W < 0 || (nnz && W && (!src || !dcol || !H0 || !sigma || !zeta || !dr2 || !h)))
+        return fail(ATO_ERR_ARG, "ato_ipm_resto_hess: arguments");
+    if (nnz == 0 || W == 0) return 0;
+    if ((nnz + RROWS - 1) / RROWS > GRID_Y_MAX) return fail(ATO_ERR_ARG, "ato_ipm_resto_hess: too many entries");
+    hipLaunchKernelGGL(k_resto_hess, dim3((W + 63) / 64, (nnz + RROWS - 1) / RROWS), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), nnz, W, src, dcol, H0, sigma, zeta, dr2, h);
+    return check_launch("ato_ipm_resto_hess");
+}
+
+int ato_ipm_resto_kkt_pack(int32_t nh, int32_t nj, int32_t n0, int32_t W, const int32_t* h_map,
+                           const int32_t* pos_orig, const int32_t* h_diag, const uint8_t* diag_new, const double* H,
+                           const double* J, double* Hb, double* Jb, double* hd, void* stream) {
+    if (nh < 0 || nj < 0 || n0 < 0 || W < 0) return fail(ATO_ERR_ARG, "ato_ipm_resto_kkt_pack: arguments");
+    if (!H) nh = n0 = 0;                          // no Hessian: only Jb is packed
+    if (W == 0 || nh + nj + n0 == 0) return 0;
+    if ((nh && (!h_map || !Hb)) || (n0 && (!h_diag || !diag_new || !hd)) || (nj && (!pos_orig || !J || !Jb)))
+        return fail(ATO_ERR_ARG, "ato_ipm_resto_kkt_pack: arguments");
+    if (((long long)nh + nj + n0 + RROWS - 1) / RROWS > GRID_Y_MAX)
+        return fail(ATO_ERR_ARG, "ato_ipm_resto_kkt_pack: too many entries");
+    hipLaunchKernelGGL(k_resto_kkt_pack, dim3((W + 63) / 64, (nh + nj + n0 + RROWS - 1) / RROWS), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), nh, nj, n0, W, h_map, pos_orig, h_diag, diag_new, H, J, Hb,
+                       Jb, hd);
+    return check_launch("ato_ipm_resto_kkt_pack");
+}
+
+int ato_ipm_resto_kkt_diag(int32_t n0, int32_t m, int32_t W, const double* dx, const double* dr, const double* hd,
+                           const uint8_t* mask, double* dxb, double* drow, double* dp, double* dn, int32_t* cnt,
+                           void* stream) {
+    if (n0 < 0 || m < 0 || W < 0) return fail(ATO_ERR_ARG, "ato_ipm_resto_kkt_diag: arguments");
+    if (W == 0) return 0;
+    if (!dx || (m && (!dr || !mask || !drow || !dp || !dn || !cnt)) || (hd && n0 && !dxb))
+        return fail(ATO_ERR_ARG, "ato_ipm_resto_kkt_diag: arguments");
+    const int nbm = (m + 255) / 256;
+    const int nbx = hd ? (n0 + RROWS - 1) / RROWS : 0;
+    if (nbm + nbx == 0) return 0;
+    if (nbm + nbx > GRID_Y_MAX) return fail(ATO_ERR_ARG, "ato_ipm_resto_kkt_diag: too many rows");
+    hipLaunchKernelGGL(k_resto_kkt_diag, dim3((W + 63) / 64, nbm + nbx), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), n0, m, W, nbm, dx, dr, hd, mask, dxb, drow, dp, dn, cnt);
+    return check_launch("ato_ipm_resto_kkt_diag");
+}
+
+int ato_ipm_resto_kkt_rhs(int32_t n0, int32_t m, int32_t W, const double* x, const double* dp, const double* dn,
+                          double* xb, void* stream) {
+    if (n0 < 0 || m < 0 || W < 0 || ((n0 + m) && W && (!x || !xb || (m && (!dp || !dn)))))
+        return fail(ATO_ERR_ARG, "ato_ipm_resto_kkt_rhs: arguments");
+    if (n0 + m == 0 || W == 0) return 0;
+    if ((n0 + m + RROWS - 1) / RROWS > GRID_Y_MAX) return fail(ATO_ERR_ARG, "ato_ipm_resto_kkt_rhs: too many rows");
+    hipLaunchKernelGGL(k_resto_kkt_rhs, dim3((W + 63) / 64, (n0 + m + RROWS - 1) / RROWS), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), n0, m, W, x, dp, dn, xb);
+    return check_launch("ato_ipm_resto_kkt_rhs");
+}
+
+int ato_ipm_resto_kkt_expand(int32_t n0, int32_t m, int32_t W, const double* xb, const double* dp, const double* dn,
+                             const uint8_t* mask, double* x, void* stream) {
+    if (n0 < 0 || m < 0 || W < 0 || ((n0 + m) && W && (!x || !xb || !mask || (m && (!dp || !dn)))))
+        return fail(ATO_ERR_ARG, "ato_ipm_resto_kkt_expand: arguments");
+    if (n0 + m == 0 || W == 0) return 0;
+    if ((n0 + m + RROWS - 1) / RROWS > GRID_Y_MAX) return fail(ATO_ERR_ARG, "ato_ipm_resto_kkt_expand: too many rows");
+    hipLaunchKernelGGL(k_resto_kkt_expand, dim3((W + 63) / 64, (n0 + m + RROWS - 1) / RROWS), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), n0, m, W, xb, dp, dn, mask, x);
+    return check_launch("ato_ipm_resto_kkt_expand");
 }
 
 }  // extern "C"

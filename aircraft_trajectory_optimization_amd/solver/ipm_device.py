@@ -63,6 +63,200 @@ def js_jty(jv, sg, y, col_ptr, src, row, want_js=True):
     return js, jty
 
 
+# ---------------------------------------------------------------------- restoration column kernels
+# (include/ato_ipm.h "The restoration phase's nested solve"): each is bit for bit the torch formulation of
+# batched_ipm.py it replaces, launched on the caller's current stream.
+def _f64(what, t, rows, W, dev=None):
+    if t.dtype != torch.float64 or t.dim() != 2 or t.shape != (rows, W) or not t.is_cuda or \
+            (dev is not None and t.device != dev):
+        raise ValueError(f'{what}: expected an fp64 [{rows}, {W}] device tensor, got {tuple(t.shape)} {t.dtype} '
+                         f'{t.device}')
+    return t.contiguous()
+
+
+def _col(what, t, W, dev):
+    if t.dtype != torch.float64 or t.shape != (W,) or t.device != dev:
+        raise ValueError(f'{what}: expected an fp64 [{W}] tensor on {dev}')
+    return t.contiguous()
+
+
+def _i32(what, t, rows, dev, dtype=torch.int32):
+    if t.dtype != dtype or t.shape != (rows,) or not t.is_contiguous() or t.device != dev:
+        raise ValueError(f'{what}: expected a contiguous {dtype} [{rows}] structure array on {dev}')
+    return t
+
+
+def _own2(what, t, rows, W, dev):
+    ''' a tensor the kernel updates in place: the caller's own contiguous storage (a copy would lose it) '''
+    if t.dtype != torch.float64 or t.shape != (rows, W) or not t.is_contiguous() or t.device != dev:
+        raise ValueError(f'{what}: expected a contiguous fp64 [{rows}, {W}] tensor on {dev}')
+    return t
+
+
+def _stream_of(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _rc(lib, rc, what):
+    if rc != 0:
+        raise RuntimeError(f'{what} failed ({rc}): {lib.ato_last_error().decode()}')
+
+
+def column_mask(instances, W, dev):
+    ''' the listed columns as a byte mask (bool [W] on dev), built on the host from the int32 list: one
+    copy, no scatter on the device '''
+    host = np.zeros(W, dtype=np.bool_)
+    idx = np.asarray(instances, dtype=np.int64).reshape(-1)
+    if len(idx) and (idx.min() < 0 or idx.max() >= W):
+        raise ValueError('instance list outside the batch')
+    host[idx] = True
+    return torch.from_numpy(host).to(dev)
+
+
+def kmul_residual(st, H, Js, dx, dr, v, rhs):
+    ''' rhs - K v, K = [[H + diag(dx), Js^T], [Js, diag(dr)]] on the structure st (batched_ipm.py _structure:
+    its int32 arrays) in one launch (ato_ipm_kmul_residual): bit for bit rhs - _Kmul(H, Js, dx, dr, v) '''
+    n, W = dx.shape
+    m = dr.shape[0]
+    dev = dx.device
+    nj, nw = int(st['n_j']), int(st['n_w'])
+    dx, dr = _f64('kmul_residual dx', dx, n, W), _f64('kmul_residual dr', dr, m, W, dev)
+    Js = _f64('kmul_residual Js', Js, nj, W, dev)
+    v, rhs = _f64('kmul_residual v', v, n + m, W, dev), _f64('kmul_residual rhs', rhs, n + m, W, dev)
+    if H is not None:
+        H = _f64('kmul_residual H', H, int(st['hr'].shape[0]), W, dev)
+    ia = [_i32('kmul_residual structure', st[k], r, dev) for k, r in
+          (('jt_ptr32', n + 1), ('jt_src32', nj), ('jt_row32', nj), ('j_ptr32', m + 1), ('jc32', nj),
+           ('w_ptr32', n + 1), ('w_src32', nw), ('w_col32', nw))]
+    out = torch.empty_like(rhs)
+    lib = native.load()
+    _rc(lib, lib.ato_ipm_kmul_residual(n, m, nj, nw, W, *[_p(t) for t in ia], _p(H), _p(Js), _p(dx), _p(dr),
+                                       _p(v), _p(rhs), _p(out), _stream_of(dev)), 'ato_ipm_kmul_residual')
+    return out
+
+
+def resto_eval(rs, X, g, jv, sg, x_ref, dr2, zeta, rho, trial=False):
+    ''' the restoration NLP's (gr, gfr, jr) at X = (x, p, nn) from the base evaluator's g and jv in one launch
+    (ato_ipm_resto_eval); trial: only gr (gfr, jr None; jv may be None). rs: the _RestorationStructure '''
+    n0, m = rs.n0, rs.m
+    W = X.shape[1]
+    dev = X.device
+    nj = int(rs.pos_orig32.shape[0])
+    X, g, sg = _f64('resto_eval X', X, n0 + 2 * m, W), _f64('resto_eval g', g, m, W, dev), \
+        _f64('resto_eval sg', sg, m, W, dev)
+    gr = torch.empty_like(g)
+    gfr = jr = None
+    if not trial:
+        jv = _f64('resto_eval jv', jv, nj, W, dev)
+        x_ref, dr2 = _f64('resto_eval x_ref', x_ref, n0, W, dev), _f64('resto_eval dr2', dr2, n0, W, dev)
+        zeta = _col('resto_eval zeta', zeta, W, dev)
+        gfr = torch.empty((n0 + 2 * m, W), dtype=torch.float64, device=dev)
+        jr = torch.empty((nj + 2 * m, W), dtype=torch.float64, device=dev)
+    else:
+        jv = x_ref = dr2 = zeta = None
+    ptr = _i32('resto_eval structure', rs.j_ptr0_32, m + 1, dev)
+    pos = _i32('resto_eval structure', rs.pos_orig32, nj, dev)
+    pe = _i32('resto_eval structure', rs.pe32, m, dev)
+    lib = native.load()
+    _rc(lib, lib.ato_ipm_resto_eval(n0, m, nj, W, 1 if trial else 0, _p(ptr), _p(pos), _p(pe), _p(X), _p(g), _p(jv),
+                                    _p(sg), _p(x_ref), _p(dr2), _p(zeta), float(rho), _p(gr), _p(gfr), _p(jr),
+                                    _stream_of(dev)), 'ato_ipm_resto_eval')
+    return gr, gfr, jr
+
+
+def resto_hess(rs, H0, sigma, zeta, dr2):
+    ''' the restoration NLP's Hessian on its expanded pattern from the base one H0 in one pass
+    (ato_ipm_resto_hess): no zero fill, scatter or gather '''
+    W = H0.shape[1]
+    dev = H0.device
+    nh0, nh = int(rs.h_map32.shape[0]), int(rs.nnz_h)
+    H0 = _f64('resto_hess H0', H0, nh0, W)
+    dr2 = _f64('resto_hess dr2', dr2, rs.n0, W, dev)
+    sigma, zeta = _col('resto_hess sigma', sigma, W, dev), _col('resto_hess zeta', zeta, W, dev)
+    src, dcol = _i32('resto_hess structure', rs.h_src32, nh, dev), _i32('resto_hess structure', rs.h_dcol32, nh, dev)
+    h = torch.empty((nh, W), dtype=torch.float64, device=dev)
+    lib = native.load()
+    _rc(lib, lib.ato_ipm_resto_hess(nh, W, _p(src), _p(dcol), _p(H0), _p(sigma), _p(zeta), _p(dr2), _p(h),
+                                    _stream_of(dev)), 'ato_ipm_resto_hess')
+    return h
+
+
+def resto_kkt_pack(rs, H, J):
+    ''' (Hb = H[h_map], Jb = J[pos_orig], hd = where(diag_new, H[h_diag], 0)) in one launch
+    (ato_ipm_resto_kkt_pack); H None: (None, Jb, None) '''
+    W = J.shape[1]
+    dev = J.device
+    nj, nh0, n0 = int(rs.pos_orig32.shape[0]), int(rs.h_map32.shape[0]), rs.n0
+    J = _f64('resto_kkt_pack J', J, nj + 2 * rs.m, W)
+    Jb = torch.empty((nj, W), dtype=torch.float64, device=dev)
+    Hb = hd = None
+    if H is not None:
+        H = _f64('resto_kkt_pack H', H, int(rs.nnz_h), W, dev)
+        Hb = torch.empty((nh0, W), dtype=torch.float64, device=dev)
+        hd = torch.empty((n0, W), dtype=torch.float64, device=dev)
+    hm, pos = _i32('resto_kkt_pack structure', rs.h_map32, nh0, dev), _i32('resto_kkt_pack structure', rs.pos_orig32,
+                                                                           nj, dev)
+    hdg = _i32('resto_kkt_pack structure', rs.h_diag32, n0, dev)
+    dnew = _i32('resto_kkt_pack structure', rs.diag_new, n0, dev, torch.bool)
+    lib = native.load()
+    _rc(lib, lib.ato_ipm_resto_kkt_pack(nh0, nj, n0, W, _p(hm), _p(pos), _p(hdg), _p(dnew), _p(H), _p(J), _p(Hb),
+                                        _p(Jb), _p(hd), _stream_of(dev)), 'ato_ipm_resto_kkt_pack')
+    return Hb, Jb, hd
+
+
+def resto_kkt_diag(n0, m, dx, dr, hd, mask, dp, dn):
+    ''' one inertia-correction pass of _RestorationKKT.factor (ato_ipm_resto_kkt_diag): (dxb, drow, cnt) from
+    dx = (dx_x, dp, dn) [n0 + 2 m, W]; the stored dp, dn [m, W] take the new values in the columns of mask
+    (bool [W]), in place. hd None (no Hessian): dxb is dx[:n0] '''
+    W = dx.shape[1]
+    dev = dx.device
+    dx, dr = _f64('resto_kkt_diag dx', dx, n0 + 2 * m, W), _f64('resto_kkt_diag dr', dr, m, W, dev)
+    _own2('resto_kkt_diag dp', dp, m, W, dev)
+    _own2('resto_kkt_diag dn', dn, m, W, dev)
+    mask = _i32('resto_kkt_diag mask', mask, W, dev, torch.bool)
+    drow = torch.empty_like(dr)
+    cnt = torch.zeros((W, 2), dtype=torch.int32, device=dev)
+    if hd is not None:
+        hd = _f64('resto_kkt_diag hd', hd, n0, W, dev)
+        dxb = torch.empty_like(hd)
+    else:
+        dxb = dx[:n0]
+    lib = native.load()
+    _rc(lib, lib.ato_ipm_resto_kkt_diag(n0, m, W, _p(dx), _p(dr), _p(hd), _p(mask), _p(dxb) if hd is not None else None,
+                                        _p(drow), _p(dp), _p(dn), _p(cnt), _stream_of(dev)),
+        'ato_ipm_resto_kkt_diag')
+    return dxb, drow, cnt
+
+
+def resto_kkt_rhs(n0, m, x, dp, dn):
+    ''' xb = [rx ; (ry + rp/dp) - rn/dn] [n0 + m, W] of x = (rx, rp, rn, ry) (ato_ipm_resto_kkt_rhs) '''
+    W = x.shape[1]
+    dev = x.device
+    x = _f64('resto_kkt_rhs x', x, n0 + 3 * m, W)
+    dp, dn = _f64('resto_kkt_rhs dp', dp, m, W, dev), _f64('resto_kkt_rhs dn', dn, m, W, dev)
+    xb = torch.empty((n0 + m, W), dtype=torch.float64, device=dev)
+    lib = native.load()
+    _rc(lib, lib.ato_ipm_resto_kkt_rhs(n0, m, W, _p(x), _p(dp), _p(dn), _p(xb), _stream_of(dev)),
+        'ato_ipm_resto_kkt_rhs')
+    return xb
+
+
+def resto_kkt_expand(n0, m, xb, dp, dn, mask, x):
+    ''' x <- [xb_x ; (rp + y)/dp ; (rn - y)/dn ; y] in the columns of mask, in place (ato_ipm_resto_kkt_expand) '''
+    W = x.shape[1]
+    dev = x.device
+    _own2('resto_kkt_expand x', x, n0 + 3 * m, W, dev)
+    if not x.is_cuda:
+        raise ValueError('resto_kkt_expand: expected device tensors')
+    xb = _f64('resto_kkt_expand xb', xb, n0 + m, W, dev)
+    dp, dn = _f64('resto_kkt_expand dp', dp, m, W, dev), _f64('resto_kkt_expand dn', dn, m, W, dev)
+    mask = _i32('resto_kkt_expand mask', mask, W, dev, torch.bool)
+    lib = native.load()
+    _rc(lib, lib.ato_ipm_resto_kkt_expand(n0, m, W, _p(xb), _p(dp), _p(dn), _p(mask), _p(x), _stream_of(dev)),
+        'ato_ipm_resto_kkt_expand')
+    return x
+
+
 class DeviceIPMKernels:
     def __init__(self, n: int, m: int, iin: torch.Tensor, ieq: torch.Tensor, device):
         self.lib = native.load()

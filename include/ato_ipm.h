@@ -201,6 +201,54 @@ int ato_ipm_resto_rows(int32_t m, int32_t W, const double* dr, const double* dp,
 int ato_ipm_js_jty(int32_t n, int32_t nnz, int32_t W, const int32_t* col_ptr, const int32_t* src, const int32_t* row,
                    const double* jv, const double* sg, const double* y, double* js, double* jty, void* stream);
 
+/* The restoration phase's nested solve (solver/batched_ipm.py _RestorationEvaluator, _RestorationKKT and the
+ * KKT residual of a backend that has none): the gathers, scatters and elementwise algebra of those wrappers as
+ * column kernels. All values fp64 [element][W] row-major, all structure arrays int32 on the device; every
+ * product, quotient and sum is rounded on its own in the order written here (no fused multiply-add), every
+ * segment sum starts from 0 and adds its entries in the given order: bit for bit the torch formulation. No
+ * kernel synchronises with the host or allocates; launches go on `stream`.
+ *
+ * ato_ipm_kmul_residual: out = rhs - K v for K = [[H + diag(dx), Js^T], [Js, diag(dr)]] on a CSR structure
+ *   (_Kmul): row i < n: rhs - ((dx_i v_i + t) + u), t = sum over column i's Jacobian entries jt_src[jt_ptr[i]
+ *   .. jt_ptr[i+1]) of Js[src] v[n + jt_row], u = sum over w_ptr[i] .. w_ptr[i+1] of H[w_src] v[w_col] (the
+ *   symmetric expansion of the lower-CSR Hessian, grouped by row; H NULL: no u); row n + r: rhs - (s + dr_r
+ *   v_{n+r}), s = sum over the row's entries e in j_ptr[r] .. j_ptr[r+1] of Js[e] v[jc[e]]. Every column.
+ * ato_ipm_resto_eval: at X = (x [n0], p [m], nn [m]) with the base evaluator's g [m] and jv [nnz_j]:
+ *   gr = (sg g - p) + nn; unless trial: gfr = [(zeta dr2)(x - x_ref) ; rho (2 m rows)] and the expanded
+ *   Jacobian jr [nnz_j + 2 m], every entry written: jv[e] sg[r] at pos_orig[e] for the entries e in j_ptr[r] ..
+ *   j_ptr[r+1] of row r, -1 at pe[r] and +1 at pe[r] + 1. zeta [W].
+ * ato_ipm_resto_hess: h[k] = (src[k] >= 0 ? H0[src[k]] : 0), and h[k] = h[k] + (sigma zeta) dr2[dcol[k]]
+ *   where dcol[k] >= 0 (the x diagonal); sigma, zeta [W].
+ * ato_ipm_resto_kkt_pack: Hb = H[h_map] [nh], Jb = J[pos_orig] [nj], hd = diag_new ? H[h_diag] : 0 [n0]
+ *   (diag_new bytes); H NULL: only Jb.
+ * ato_ipm_resto_kkt_diag: from dx = (dx_x [n0], dp [m], dn [m]) and dr [m]: dxb = dx_x + hd (hd NULL: not
+ *   written), drow = (dr - 1/dp) - 1/dn, cnt (int32 [W][2], ADDED to: zero it first) += (number of dp, dn > 0,
+ *   number < 0), and the stored dp, dn [m] replaced by the new ones in the columns with mask (bytes [W]) set.
+ * ato_ipm_resto_kkt_rhs: xb [n0 + m] = [rx ; (ry + rp/dp) - rn/dn] of x = (rx [n0], rp [m], rn [m], ry [m]).
+ * ato_ipm_resto_kkt_expand: in the columns with mask set, x = [xb_x ; (rp + y)/dp ; (rn - y)/dn ; y] with
+ *   y = xb[n0:], rp and rn the values x held; the other columns are not touched. */
+int ato_ipm_kmul_residual(int32_t n, int32_t m, int32_t nnz_j, int32_t nnz_w, int32_t W, const int32_t* jt_ptr,
+                          const int32_t* jt_src, const int32_t* jt_row, const int32_t* j_ptr, const int32_t* jc,
+                          const int32_t* w_ptr, const int32_t* w_src, const int32_t* w_col, const double* H,
+                          const double* Js, const double* dx, const double* dr, const double* v, const double* rhs,
+                          double* out, void* stream);
+int ato_ipm_resto_eval(int32_t n0, int32_t m, int32_t nnz_j, int32_t W, int32_t trial, const int32_t* j_ptr,
+                       const int32_t* pos_orig, const int32_t* pe, const double* X, const double* g,
+                       const double* jv, const double* sg, const double* x_ref, const double* dr2,
+                       const double* zeta, double rho, double* gr, double* gfr, double* jr, void* stream);
+int ato_ipm_resto_hess(int32_t nnz, int32_t W, const int32_t* src, const int32_t* dcol, const double* H0,
+                       const double* sigma, const double* zeta, const double* dr2, double* h, void* stream);
+int ato_ipm_resto_kkt_pack(int32_t nh, int32_t nj, int32_t n0, int32_t W, const int32_t* h_map,
+                           const int32_t* pos_orig, const int32_t* h_diag, const uint8_t* diag_new, const double* H,
+                           const double* J, double* Hb, double* Jb, double* hd, void* stream);
+int ato_ipm_resto_kkt_diag(int32_t n0, int32_t m, int32_t W, const double* dx, const double* dr, const double* hd,
+                           const uint8_t* mask, double* dxb, double* drow, double* dp, double* dn, int32_t* cnt,
+                           void* stream);
+int ato_ipm_resto_kkt_rhs(int32_t n0, int32_t m, int32_t W, const double* x, const double* dp, const double* dn,
+                          double* xb, void* stream);
+int ato_ipm_resto_kkt_expand(int32_t n0, int32_t m, int32_t W, const double* xb, const double* dp, const double* dn,
+                             const uint8_t* mask, double* x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

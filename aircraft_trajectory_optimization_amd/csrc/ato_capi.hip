@@ -56,6 +56,8 @@ static void release(ato_handle* h) {
     (void)hipFree(h->d_dgf);
     (void)hipFree(h->d_lift);
     (void)hipFree(h->d_replay_w);
+    for (auto& kv : h->remesh_tabs) (void)hipFree(kv.second.dev);
+    h->remesh_tabs.clear();
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
     h->events.clear();
 }
@@ -456,6 +458,43 @@ static int replay_impl(ato_handle* h, int32_t batch, int32_t layout, const doubl
 extern "C" int ato_replay(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t substeps,
                           double* zsim, double* err, double* traj, void* stream) {
     ATO_NOEXCEPT_BODY(replay_impl(h, batch, layout, w, substeps, zsim, err, traj, stream))
+}
+
+static int remesh_impl(ato_handle* src, ato_handle* dst, int32_t batch_src, int32_t batch_dst, int32_t layout,
+                       const double* w_src, const int32_t* cols, double* w_dst, void* stream) {
+    if (!src || !dst) return fail(ATO_ERR_ARG, "null handle");
+    const ato::ProbD &ps = src->pd, &pd = dst->pd;
+    const char* msg = "";
+    if (int rc = ato::remesh_check(ps, pd, batch_src, batch_dst, cols != nullptr, layout, &msg)) return fail(rc, msg);
+    if (!w_src || !w_dst) return fail(ATO_ERR_ARG, "null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    const int r = pd.N / ps.N;
+    std::vector<double> key{(double)r};
+    key.insert(key.end(), ps.tau, ps.tau + ps.K1);
+    ato_handle::RemeshTable& tab = dst->remesh_tabs[key];
+    if (!tab.dev) {
+        tab.host.resize((size_t)r * pd.K1 * ps.K1);
+        ato::remesh_weights(ps.tau, ps.K1, pd.tau, pd.K1, r, tab.host.data());
+        const size_t bytes = tab.host.size() * sizeof(double);
+        if (hipMalloc((void**)&tab.dev, bytes) != hipSuccess) {
+            tab.dev = nullptr;
+            return fail(ATO_ERR_HIP, "remesh weight table: out of device memory");
+        }
+        if (hipMemcpyAsync(tab.dev, tab.host.data(), bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
+            (void)hipFree(tab.dev);
+            tab.dev = nullptr;
+            return fail(ATO_ERR_HIP, "remesh weight table: upload failed");
+        }
+    }
+    const ato::RemeshD a = ato::remesh_args(ps, pd, tab.dev);
+    const hipError_t e = ato::launch_remesh(a, batch_src, batch_dst, layout, w_src, cols, w_dst, st);
+    if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("remesh launch: ") + hipGetErrorString(e));
+    return ATO_OK;
+}
+
+extern "C" int ato_remesh(ato_handle* src, ato_handle* dst, int32_t batch_src, int32_t batch_dst, int32_t layout,
+                          const double* w_src, const int32_t* cols, double* w_dst, void* stream) {
+    ATO_NOEXCEPT_BODY(remesh_impl(src, dst, batch_src, batch_dst, layout, w_src, cols, w_dst, stream))
 }
 
 extern "C" int ato_eval(ato_handle* h, int32_t batch, int32_t layout, const double* w, double* g,

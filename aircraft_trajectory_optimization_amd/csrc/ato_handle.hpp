@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include "ato_kernels.hpp"
 #include "ato_replay.hpp"
+#include "ato_remesh.hpp"
 
 struct ato_handle {
     ato::Layout L;
@@ -55,4 +56,12 @@ struct ato_handle {
     double* d_replay_w = nullptr;
     int32_t replay_S = 0;
     std::map<int32_t, std::vector<double>> replay_w_host;
+    // mesh transfer INTO this problem (ato_remesh.hpp): one weight table [r][K' + 1][K + 1] per source
+    // discretisation, keyed by (r, the source's tau_0 .. tau_K); allocated and uploaded by the first call
+    // with that key, on that call's stream, and never rewritten or freed before the handle
+    struct RemeshTable {
+        std::vector<double> host;
+        double* dev = nullptr;
+    };
+    std::map<std::vector<double>, RemeshTable> remesh_tabs;
 };

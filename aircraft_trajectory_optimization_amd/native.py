@@ -117,7 +117,7 @@ EXPORTED_SYMBOLS = ('ato_create', 'ato_destroy', 'ato_sizes', 'ato_sparsity', 'a
                     'ato_kkt_create', 'ato_kkt_destroy', 'ato_kkt_reserve', 'ato_kkt_factor', 'ato_kkt_solve',
                     'ato_kkt_residual', 'ato_kkt_residual_list', 'ato_set_instance_spheres',
                     'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity', 'ato_replay_set_lift',
-                    'ato_replay') + IPM_SYMBOLS
+                    'ato_replay', 'ato_remesh') + IPM_SYMBOLS
 
 
 def library_path() -> str:
@@ -155,6 +155,7 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
         lib.ato_gradf_sparsity.argtypes = [vp, i32p, i32p]
         lib.ato_replay_set_lift.argtypes = [vp, vp]
         lib.ato_replay.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, vp, vp]
+        lib.ato_remesh.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp]
         lib.ato_kkt_create.argtypes = [vp, ctypes.POINTER(vp)]
         lib.ato_kkt_destroy.argtypes = [vp]
         lib.ato_kkt_reserve.argtypes = [vp, ctypes.c_int32]
@@ -199,7 +200,7 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
                    'ato_eval', 'ato_eval_f32', 'ato_hess_sparsity', 'ato_hess_eval', 'ato_timing',
                    'ato_timing_read', 'ato_timing_stride', 'ato_mesh_create', 'ato_mesh_destroy', 'ato_mesh_signed_distance',
                    'ato_set_instance_spheres', 'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity',
-                   'ato_replay_set_lift', 'ato_replay'):
+                   'ato_replay_set_lift', 'ato_replay', 'ato_remesh'):
             getattr(lib, fn).restype = ctypes.c_int
     return lib
 
@@ -422,6 +423,26 @@ class NativeProblem:
         message.
         '''
         rc = self.replay_rc(batch, w, substeps, zsim, err, traj, layout, stream)
+        if rc == ATO_ERR_UNSUPPORTED:
+            raise NotImplementedError(self.lib.ato_last_error().decode())
+        self._check(rc)
+
+    def remesh_rc(self, src: 'NativeProblem', batch_src: int, batch_dst: int, w_src: int, w_dst: int, cols: int = 0,
+                  layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0) -> int:
+        ''' ato_remesh(src -> this problem) on device pointers; returns the library's code '''
+        return self.lib.ato_remesh(src.handle, self.handle, int(batch_src), int(batch_dst), int(layout),
+                                   w_src or None, cols or None, w_dst or None, stream or None)
+
+    def remesh_ptrs(self, src: 'NativeProblem', batch_src: int, batch_dst: int, w_src: int, w_dst: int,
+                    cols: int = 0, layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0):
+        '''
+        Transfer the decision vectors w_src [src.nw x batch_src] of the problem `src` to this problem's
+        discretisation, w_dst [nw x batch_dst] (asynchronous on `stream`): N a multiple of src's, any
+        degree. cols: device int32 [batch_dst], the source column of every destination column, or 0 for
+        the identity. Problems the transfer does not cover (RK4 transcription, CPC variables) raise
+        NotImplementedError with the library's message.
+        '''
+        rc = self.remesh_rc(src, batch_src, batch_dst, w_src, w_dst, cols, layout, stream)
         if rc == ATO_ERR_UNSUPPORTED:
             raise NotImplementedError(self.lib.ato_last_error().decode())
         self._check(rc)

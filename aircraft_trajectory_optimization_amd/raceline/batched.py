@@ -163,6 +163,39 @@ class BatchedNLP:
                                  traj.data_ptr() if trajectory else 0, layout=self.layout, stream=st.cuda_stream)
         return zsim, err, traj
 
+    def remesh_from(self, src: 'BatchedNLP', W_src, cols=None, stream=None) -> torch.Tensor:
+        '''
+        Transfer decision vectors of the batch `src` (the same scenario on a coarser mesh: this N a multiple
+        of src's, any degree) to this batch's discretisation (ato_remesh, asynchronous on `stream`):
+        h' = h / r, every node variable by the Lagrange interpolant of its source interval. W_src: fp64
+        device tensor in src's layout ((nw, B) interleaved, (B, nw) instance-major) or a host array
+        (B, nw). cols: the source column of every column of this batch (int tensor or sequence of length
+        self.batch), None for the identity. Returns W in this batch's layout. Both batches share one
+        layout. Problems the transfer does not cover raise NotImplementedError.
+        '''
+        if src.layout != self.layout:
+            raise ValueError('source and destination batches must share one layout')
+        il = self.layout == native.ATO_LAYOUT_INTERLEAVED
+        Bs, Bd = src.batch, self.batch
+        if not torch.is_tensor(W_src):
+            t = torch.as_tensor(np.array(W_src, np.float64).reshape(Bs, -1))
+            W_src = (t.T.contiguous() if il else t.contiguous()).to(self.device)
+        if W_src.dtype != torch.float64 or \
+                tuple(W_src.shape) != ((src.problem.nw, Bs) if il else (Bs, src.problem.nw)):
+            raise ValueError("W_src must be fp64 in the layout of the source batch")
+        W_src = W_src.to(self.device).contiguous()
+        if cols is not None:
+            cols = torch.as_tensor(cols).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(cols.shape) != (Bd,):
+                raise ValueError(f'cols must have one entry per destination column ({Bd})')
+        W = torch.empty((self.problem.nw, Bd) if il else (Bd, self.problem.nw), device=self.device,
+                        dtype=torch.float64)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self.problem.remesh_ptrs(src.problem, Bs, Bd, W_src.data_ptr(), W.data_ptr(),
+                                 cols.data_ptr() if cols is not None else 0, layout=self.layout,
+                                 stream=st.cuda_stream)
+        return W
+
     def _host(self, t: torch.Tensor) -> np.ndarray:
         a = t.detach().to('cpu', torch.float64).numpy()
         return a.T.copy() if self.layout == native.ATO_LAYOUT_INTERLEAVED else a

@@ -218,6 +218,29 @@ int ato_replay_set_lift(ato_handle* h, const double* lift);
 int ato_replay(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t substeps,
                double* zsim, double* err, double* traj, void* stream);
 
+/* Transfer of decision vectors between two discretisations of one scenario (csrc/ato_remesh.hpp). src has
+ * N intervals of degree K, dst N' = r N intervals of degree K' (r >= 1 an integer; K' >= 1, possibly below
+ * K), both collocation transcriptions of the same model variant (model, attitude, frame). Per instance
+ *   h'[n r + j]     = h[n] / r
+ *   v'[n r + j, k'] = sum_m l_m((j + tau'_k') / r) v[n, m]     for every per-node variable (states, inputs,
+ *                                                              input rates)
+ * with l_m the Lagrange basis over the source nodes tau_0 = 0, tau_1 .. tau_K (the interpolant of the replay's
+ * input), evaluated by the product formula of the replay's weights, summed in ascending m. For K' >= K the
+ * piecewise polynomial as a function of time is unchanged; r = 1, K' = K copies finite inputs bit for bit.
+ * Nothing is renormalised or clipped, multipliers are not transferred, and feasibility on the new mesh is not
+ * preserved: the result is a start for a warm solve.
+ *
+ * w_src [nw x batch_src], w_dst [nw' x batch_dst], both in `layout`. cols: device array [batch_dst], the source
+ * column of every destination column, or NULL for the identity (then batch_dst == batch_src). A destination
+ * column whose entry is outside [0, batch_src) is left unwritten. Asynchronous on stream; no device-wide
+ * synchronisation. The weight table [r][K'+1][K+1] lives on dst, one per source discretisation: the first call
+ * with a new one allocates it and uploads it on that call's stream (calls on other streams are the caller's
+ * to order after it); no other call allocates.
+ * ATO_ERR_ARG: N' not a multiple of N or below it, batch < 1, unknown layout, different model variant;
+ * ATO_ERR_UNSUPPORTED: an RK4-transcribed problem, or one that carries CPC progress variables. */
+int ato_remesh(ato_handle* src, ato_handle* dst, int32_t batch_src, int32_t batch_dst, int32_t layout,
+               const double* w_src, const int32_t* cols, double* w_dst, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the evaluation stream. ato_timing(h, n)
  * allocates n event slots and starts recording (n = 0 stops); while on, each ato_eval
  * records events around its Jacobian kernel and its cost-reduction kernel. ato_timing_read

@@ -1,0 +1,129 @@
+'''
+Mesh-transfer test fixtures: the CPU twin of the transfer kernel (tests/native/remesh_hostcheck.cpp),
+the cases the CPU and the GPU tests share, and their specs.
+'''
+import ctypes
+import functools
+import os
+import subprocess
+
+import numpy as np
+
+from aircraft_trajectory_optimization_amd import native
+from tests.helpers import REPO, product_spec
+from tests.replay_helpers import FRAMES, MODELS
+
+REMESH_SRC = os.path.join(REPO, 'tests', 'native', 'remesh_hostcheck.cpp')
+REMESH_LIB = os.path.join(REPO, 'tests', 'native', 'libato_remeshcheck.so')
+
+# Twin / device against the numpy oracle, relative to max(1, |value|), over every case below in both
+# layouts. Measured once on the CPU twin: 1.2212e-15 (the largest over all 54 cases, at esp-global-K2to9-r1:
+# the twin sums with fused multiply-adds, the oracle rounds every product); the bound is 10 x that (it may
+# not exceed 1e-12).
+REMESH_TOL = 1.2212e-14
+
+FRAMES = {**FRAMES, 'relative': dict(frame='parametric', N=3, global_r=False)}
+# (K, K', r)
+TRANSFERS = [(1, 1, 2), (2, 3, 1), (2, 2, 3), (9, 9, 2), (3, 1, 2), (2, 9, 1)]
+CASES = [(m, f, *t) for m in MODELS for f in ('global', 'parametric') for t in TRANSFERS] + \
+        [('esp', 'relative', *t) for t in TRANSFERS]
+
+
+def case_id(c):
+    return f'{c[0]}-{c[1]}-K{c[2]}to{c[3]}-r{c[4]}'
+
+
+def build_remeshcheck(force=False):
+    ''' the twin, with the g++ line of helpers.build_hostcheck '''
+    csrc = os.path.join(REPO, 'aircraft_trajectory_optimization_amd', 'csrc')
+    srcs = [REMESH_SRC] + [os.path.join(csrc, f) for f in ('ato_models.hpp', 'ato_dual.hpp', 'ato_program.hpp',
+                                                          'ato_layout.hpp', 'ato_remesh.hpp')]
+    if not force and os.path.exists(REMESH_LIB) and \
+            os.path.getmtime(REMESH_LIB) >= max(os.path.getmtime(s) for s in srcs):
+        return REMESH_LIB
+    subprocess.check_call(['g++', '-std=c++20', '-O3', '-march=x86-64-v3', '-fopenmp', '-fPIC', '-shared', '-o',
+                           REMESH_LIB, REMESH_SRC])
+    return REMESH_LIB
+
+
+@functools.lru_cache(maxsize=None)
+def _lib():
+    lib = ctypes.CDLL(build_remeshcheck())
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.atom_create.argtypes = [ctypes.POINTER(native.AtoProblemDesc), ctypes.POINTER(vp)]
+    lib.atom_last_error.restype = ctypes.c_char_p
+    lib.atom_destroy.argtypes = [vp]
+    lib.atom_weights.argtypes = [vp, vp, vp]
+    lib.atom_remesh.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp]
+    return lib
+
+
+class _Problem:
+    def __init__(self, spec):
+        self.lib, self.spec = _lib(), spec
+        self.holder = native.DescHolder(spec.native_spec())
+        h = ctypes.c_void_p()
+        if self.lib.atom_create(ctypes.byref(self.holder.desc), ctypes.byref(h)) != 0:
+            raise RuntimeError(self.lib.atom_last_error().decode())
+        self.h = h
+
+    def __del__(self):
+        try:
+            self.lib.atom_destroy(self.h)
+        except Exception:  # pylint: disable=broad-except
+            pass
+
+
+class RemeshTwin:
+    ''' ato_remesh on host arrays (CPU build of csrc/ato_remesh.hpp) '''
+
+    def __init__(self, src, dst):
+        self.lib, self.src, self.dst = _lib(), _Problem(src), _Problem(dst)
+
+    def weights(self):
+        s, d = self.src.spec, self.dst.spec
+        wt = np.zeros((d.N // s.N, d.K1, s.K1))
+        self.lib.atom_weights(self.src.h, self.dst.h, wt.ctypes.data)
+        return wt
+
+    def last_error(self):
+        return self.lib.atom_last_error().decode()
+
+    def remesh_rc(self, W, cols=None, layout=native.ATO_LAYOUT_INSTANCE_MAJOR, out=None, batch_dst=None,
+                  batch_src=None):
+        '''
+        W (B, nw) -> (rc, W' (B', nw')). out: the (B', nw') array the destination starts from (the twin
+        writes over it; default zeros). batch_src / batch_dst: the batch arguments, where they shall differ
+        from the arrays' rows.
+        '''
+        W = np.ascontiguousarray(np.atleast_2d(W), np.float64)
+        Bs = W.shape[0]
+        Bd = len(cols) if cols is not None else Bs
+        il = layout == native.ATO_LAYOUT_INTERLEAVED
+        res = np.zeros((Bd, self.dst.spec.nw)) if out is None else np.array(out, np.float64)
+        win = np.ascontiguousarray(W.T) if il else W
+        wout = np.ascontiguousarray(res.T) if il else np.ascontiguousarray(res)
+        c = None if cols is None else np.ascontiguousarray(cols, np.int32)
+        rc = self.lib.atom_remesh(self.src.h, self.dst.h, Bs if batch_src is None else batch_src,
+                                  Bd if batch_dst is None else batch_dst, layout, win.ctypes.data,
+                                  None if c is None else c.ctypes.data, wout.ctypes.data)
+        return rc, (wout.T.copy() if il else wout)
+
+    def remesh(self, W, **kw):
+        rc, out = self.remesh_rc(W, **kw)
+        if rc != 0:
+            raise RuntimeError(f'twin remesh error {rc}: {self.last_error()}')
+        return out
+
+
+@functools.lru_cache(maxsize=None)
+def mesh_spec(model, frame, N, K, **kw):
+    ''' the race-track spec of a model / frame at N intervals of degree K '''
+    return product_spec(track='race', K=K, **{**MODELS[model], **FRAMES[frame], 'N': N, **kw})
+
+
+def case_specs(c):
+    ''' (source, destination) specs of a case: N = 3 (the global frame rounds it up to 7), N' = r N '''
+    model, frame, K, Kd, r = c
+    src = mesh_spec(model, frame, FRAMES[frame]['N'], K)
+    return src, mesh_spec(model, frame, src.N * r, Kd)

@@ -57,6 +57,9 @@ static void release(ato_handle* h) {
     (void)hipFree(h->d_lift);
     (void)hipFree(h->d_replay_w);
     for (auto& kv : h->remesh_tabs) (void)hipFree(kv.second.dev);
+    (void)hipFree(h->d_line);
+    (void)hipFree(h->d_clear_w);
+    (void)hipFree(h->d_clear_pos);
     h->remesh_tabs.clear();
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
     h->events.clear();
@@ -135,6 +138,13 @@ static int create_impl(const ato_problem_desc* desc, ato_handle** out) {
         release(h);
         delete h;
         return fail(ATO_ERR_HIP, "replay weight table: out of device memory");
+    }
+    // the clearance's weight table likewise
+    if (hipMalloc((void**)&h->d_clear_w, (size_t)(ato::CLEAR_SMAX + 1) * (ATO_KMAX + 1) * sizeof(double)) !=
+        hipSuccess) {
+        release(h);
+        delete h;
+        return fail(ATO_ERR_HIP, "clearance weight table: out of device memory");
     }
     h->pd = h->L.p;
     h->pd.geom = h->d_geom;
@@ -495,6 +505,83 @@ static int remesh_impl(ato_handle* src, ato_handle* dst, int32_t batch_src, int3
 extern "C" int ato_remesh(ato_handle* src, ato_handle* dst, int32_t batch_src, int32_t batch_dst, int32_t layout,
                           const double* w_src, const int32_t* cols, double* w_dst, void* stream) {
     ATO_NOEXCEPT_BODY(remesh_impl(src, dst, batch_src, batch_dst, layout, w_src, cols, w_dst, stream))
+}
+
+static int clearance_set_line_impl(ato_handle* h, const ato_line_table* t) {
+    if (!h || !t) return fail(ATO_ERR_ARG, "null argument");
+    if (h->L.p.frame == ato::GLOBAL) return ATO_OK;      // not needed: ignored
+    if (t->n_xc < 2 || t->n_ry < 2 || !t->xc_knots || !t->xc_coef || !t->ry_knots || !t->ry_coef)
+        return fail(ATO_ERR_ARG, "bad centreline table");
+    const size_t nx = (size_t)t->n_xc, nr = (size_t)t->n_ry;
+    std::vector<double> buf;
+    buf.insert(buf.end(), t->xc_knots, t->xc_knots + nx);
+    buf.insert(buf.end(), t->xc_coef, t->xc_coef + (nx + 1) * 12);
+    buf.insert(buf.end(), t->ry_knots, t->ry_knots + nr);
+    buf.insert(buf.end(), t->ry_coef, t->ry_coef + (nr + 1) * 12);
+    double* d = nullptr;
+    ATO_HIP(hipMalloc((void**)&d, buf.size() * sizeof(double)));
+    if (hipMemcpy(d, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return fail(ATO_ERR_HIP, "centreline table: upload failed");
+    }
+    if (hipDeviceSynchronize() != hipSuccess) {      // a queued clearance may still read the table this one replaces
+        (void)hipFree(d);
+        return fail(ATO_ERR_HIP, "centreline table: device synchronisation failed");
+    }
+    (void)hipFree(h->d_line);
+    h->d_line = d;
+    h->line = ato::LineD{t->n_xc, t->n_ry, d, d + nx, d + nx + (nx + 1) * 12, d + nx + (nx + 1) * 12 + nr};
+    return ATO_OK;
+}
+
+extern "C" int ato_clearance_set_line(ato_handle* h, const ato_line_table* t) {
+    ATO_NOEXCEPT_BODY(clearance_set_line_impl(h, t))
+}
+
+static int clearance_impl(ato_handle* h, ato_mesh* mesh, int32_t batch, int32_t layout, const double* w,
+                          int32_t samples, double* pos, double* dist, int32_t cull, void* stream) {
+    if (!h) return fail(ATO_ERR_ARG, "null handle");
+    const ato::ProbD& p = h->pd;
+    const char* msg = "";
+    if (int rc = ato::clearance_check(p, h->d_line != nullptr, batch, layout, samples, &msg)) return fail(rc, msg);
+    if (!w || (!pos && !dist)) return fail(ATO_ERR_ARG, "null buffer");
+    if (dist && !mesh) return fail(ATO_ERR_ARG, "distances need a mesh");
+    if (cull != 0 && cull != 1) return fail(ATO_ERR_ARG, "cull must be 0 or 1");
+    hipStream_t st = (hipStream_t)stream;
+    const int S1 = ato::clearance_points(p.K1, samples);
+    const size_t npts = (size_t)p.N * S1 * batch;
+    if (!pos) {
+        if (h->clear_pos_len < 3 * npts) {
+            // the one allocation of this call path: hipFree waits for the work that still reads the old buffer
+            (void)hipFree(h->d_clear_pos);
+            h->d_clear_pos = nullptr;
+            h->clear_pos_len = 0;
+            ATO_HIP(hipMalloc((void**)&h->d_clear_pos, 3 * npts * sizeof(double)));
+            h->clear_pos_len = 3 * npts;
+        }
+        pos = h->d_clear_pos;
+    }
+    if (h->clear_samples != samples) {
+        std::vector<double>& tab = h->clear_w_host[samples];
+        if (tab.empty()) {
+            tab.resize((size_t)S1 * p.K1);
+            ato::clearance_weights(p.tau, p.K1, samples, tab.data());
+        }
+        ATO_HIP(hipMemcpyAsync(h->d_clear_w, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        h->clear_samples = samples;
+    }
+    const ato::ClearD a = ato::clearance_args(p, samples, h->d_clear_w, h->line);
+    const hipError_t e = ato::launch_clearance_pos(a, batch, layout, w, pos, st);
+    if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("clearance launch: ") + hipGetErrorString(e));
+    if (!dist) return ATO_OK;
+    const bool il = layout == ATO_LAYOUT_INTERLEAVED;
+    return ato_mesh_signed_distance_strided(mesh, (int64_t)npts, pos, il ? 1 : 3, il ? (int64_t)npts : 1, dist, cull,
+                                            stream);
+}
+
+extern "C" int ato_clearance(ato_handle* h, ato_mesh* mesh, int32_t batch, int32_t layout, const double* w,
+                             int32_t samples, double* pos, double* dist, int32_t cull, void* stream) {
+    ATO_NOEXCEPT_BODY(clearance_impl(h, mesh, batch, layout, w, samples, pos, dist, cull, stream))
 }
 
 extern "C" int ato_eval(ato_handle* h, int32_t batch, int32_t layout, const double* w, double* g,

@@ -6,6 +6,7 @@
 #include "ato_kernels.hpp"
 #include "ato_replay.hpp"
 #include "ato_remesh.hpp"
+#include "ato_clearance.hpp"
 
 struct ato_handle {
     ato::Layout L;
@@ -64,4 +65,15 @@ struct ato_handle {
         double* dev = nullptr;
     };
     std::map<std::vector<double>, RemeshTable> remesh_tabs;
+    // clearance (ato_clearance.hpp): the centreline's two piecewise cubics (ato_clearance_set_line, one
+    // allocation: knots and coefficients back to back), the weight table of the sample count last used (sized
+    // for CLEAR_SMAX, uploaded from per-count host tables that are never rewritten) and the position buffer of
+    // calls that pass pos = NULL (grown only when a call needs more)
+    double* d_line = nullptr;
+    ato::LineD line{};
+    double* d_clear_w = nullptr;
+    int32_t clear_samples = -1;
+    std::map<int32_t, std::vector<double>> clear_w_host;
+    double* d_clear_pos = nullptr;
+    size_t clear_pos_len = 0;
 };

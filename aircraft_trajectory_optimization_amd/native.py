@@ -92,6 +92,23 @@ class AtoProblemDesc(ctypes.Structure):
     ]
 
 
+class AtoLineTable(ctypes.Structure):
+    ''' mirror of ato_line_table '''
+    _fields_ = [('n_xc', ctypes.c_int32), ('n_ry', ctypes.c_int32), ('xc_knots', ctypes.c_void_p),
+                ('xc_coef', ctypes.c_void_p), ('ry_knots', ctypes.c_void_p), ('ry_coef', ctypes.c_void_p)]
+
+
+def line_table_struct(table: dict):
+    ''' (AtoLineTable, the arrays it points at) of a ProblemSpec.line_table() '''
+    keep = {k: np.ascontiguousarray(table[k], dtype=np.float64) for k in ('xc_knots', 'xc_coef', 'ry_knots', 'ry_coef')}
+    for kn, co in (('xc_knots', 'xc_coef'), ('ry_knots', 'ry_coef')):
+        if keep[kn].ndim != 1 or keep[co].shape != (len(keep[kn]) + 1, 4, 3):
+            raise ValueError(f'{co} must be (len({kn}) + 1, 4, 3), got {keep[co].shape}')
+    t = AtoLineTable(len(keep['xc_knots']), len(keep['ry_knots']), keep['xc_knots'].ctypes.data,
+                     keep['xc_coef'].ctypes.data, keep['ry_knots'].ctypes.data, keep['ry_coef'].ctypes.data)
+    return t, keep
+
+
 class AtoIpmDims(ctypes.Structure):
     ''' include/ato_ipm.h ato_ipm_dims '''
     _fields_ = [('n', ctypes.c_int32), ('m', ctypes.c_int32), ('mi', ctypes.c_int32), ('meq', ctypes.c_int32),
@@ -117,7 +134,8 @@ EXPORTED_SYMBOLS = ('ato_create', 'ato_destroy', 'ato_sizes', 'ato_sparsity', 'a
                     'ato_kkt_create', 'ato_kkt_destroy', 'ato_kkt_reserve', 'ato_kkt_factor', 'ato_kkt_solve',
                     'ato_kkt_residual', 'ato_kkt_residual_list', 'ato_set_instance_spheres',
                     'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity', 'ato_replay_set_lift',
-                    'ato_replay', 'ato_remesh') + IPM_SYMBOLS
+                    'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided', 'ato_clearance_set_line',
+                    'ato_clearance') + IPM_SYMBOLS
 
 
 def library_path() -> str:
@@ -156,6 +174,11 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
         lib.ato_replay_set_lift.argtypes = [vp, vp]
         lib.ato_replay.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, vp, vp]
         lib.ato_remesh.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp]
+        lib.ato_mesh_signed_distance_strided.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int64, vp,
+                                                         ctypes.c_int32, vp]
+        lib.ato_clearance_set_line.argtypes = [vp, ctypes.POINTER(AtoLineTable)]
+        lib.ato_clearance.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp,
+                                      ctypes.c_int32, vp]
         lib.ato_kkt_create.argtypes = [vp, ctypes.POINTER(vp)]
         lib.ato_kkt_destroy.argtypes = [vp]
         lib.ato_kkt_reserve.argtypes = [vp, ctypes.c_int32]
@@ -200,7 +223,8 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
                    'ato_eval', 'ato_eval_f32', 'ato_hess_sparsity', 'ato_hess_eval', 'ato_timing',
                    'ato_timing_read', 'ato_timing_stride', 'ato_mesh_create', 'ato_mesh_destroy', 'ato_mesh_signed_distance',
                    'ato_set_instance_spheres', 'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity',
-                   'ato_replay_set_lift', 'ato_replay', 'ato_remesh'):
+                   'ato_replay_set_lift', 'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided',
+                   'ato_clearance_set_line', 'ato_clearance'):
             getattr(lib, fn).restype = ctypes.c_int
     return lib
 
@@ -443,6 +467,31 @@ class NativeProblem:
         NotImplementedError with the library's message.
         '''
         rc = self.remesh_rc(src, batch_src, batch_dst, w_src, w_dst, cols, layout, stream)
+        if rc == ATO_ERR_UNSUPPORTED:
+            raise NotImplementedError(self.lib.ato_last_error().decode())
+        self._check(rc)
+
+    def clearance_set_line(self, table: dict):
+        ''' centreline table of a parametric problem (ProblemSpec.line_table), copied '''
+        t, _keep = line_table_struct(table)
+        self._check(self.lib.ato_clearance_set_line(self.handle, ctypes.byref(t)))
+
+    def clearance_rc(self, batch: int, w: int, samples: int, pos: int = 0, dist: int = 0, mesh=None, cull: int = 0,
+                     layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0) -> int:
+        ''' ato_clearance on device pointers; returns the library's code (ato_last_error has the message) '''
+        return self.lib.ato_clearance(self.handle, mesh, int(batch), int(layout), w or None, int(samples),
+                                      pos or None, dist or None, int(cull), stream or None)
+
+    def clearance_ptrs(self, batch: int, w: int, samples: int, pos: int = 0, dist: int = 0, mesh=None, cull: int = 0,
+                       layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0):
+        '''
+        Dense global positions of the decision vectors w and their signed distance to a mesh (asynchronous on
+        `stream`): S1 = samples + 1 points per interval (samples = 0: the K + 1 nodes); pos [3 x N S1 batch]
+        (interleaved) or [N S1 batch x 3], dist [N S1 batch], either may be 0; mesh: an ato_mesh handle
+        (MeshObstacle.handle), needed for dist. RK4-transcribed problems raise NotImplementedError with the
+        library's message.
+        '''
+        rc = self.clearance_rc(batch, w, samples, pos, dist, mesh, cull, layout, stream)
         if rc == ATO_ERR_UNSUPPORTED:
             raise NotImplementedError(self.lib.ato_last_error().decode())
         self._check(rc)

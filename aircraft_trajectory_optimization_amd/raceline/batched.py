@@ -163,6 +163,50 @@ class BatchedNLP:
                                  traj.data_ptr() if trajectory else 0, layout=self.layout, stream=st.cuda_stream)
         return zsim, err, traj
 
+    def clearance(self, mesh, W=None, samples: int = 16, cull: Optional[bool] = None, positions: bool = True,
+                  stream=None):
+        '''
+        Dense global positions of decision vectors and their signed distance to an obstacle mesh
+        (ato_clearance, asynchronous on `stream`): per interval S1 = samples + 1 points of the collocation
+        polynomial at i / samples (samples = 0: the K + 1 nodes, the reference's collision test), parametric
+        problems placed through the centreline at the sample's own s. mesh: a MeshObstacle, or None for the
+        positions alone. W as in replay(). cull: tile culling of the distance kernel (None: the measured
+        default, obstacles.mesh_obstacle.DEFAULT_CULL); it does not change the result. Returns (pos, dist) in
+        the layout: interleaved (3, N, S1, B), (N, S1, B); instance-major (B, N, S1, 3), (B, N, S1); dist is
+        None without a mesh; positions=False keeps the positions in a buffer of the library and returns None
+        for them. RK4-transcribed problems raise NotImplementedError.
+        '''
+        from aircraft_trajectory_optimization_amd.obstacles.mesh_obstacle import DEFAULT_CULL
+        sp_, B = self.spec, self.batch
+        il = self.layout == native.ATO_LAYOUT_INTERLEAVED
+        if W is None:
+            if self.w is None or self.fp32:
+                raise TypeError('clearance needs fp64 decision vectors (pass W)')
+            W = self.w
+        elif not torch.is_tensor(W):
+            t = torch.as_tensor(np.array(W, np.float64).reshape(B, -1))
+            W = (t.T.contiguous() if il else t.contiguous()).to(self.device)
+        if W.dtype != torch.float64 or tuple(W.shape) != ((self.problem.nw, B) if il else (B, self.problem.nw)):
+            raise ValueError('W must be fp64 in the layout of this batch')
+        W = W.contiguous()
+        if mesh is None and not positions:
+            raise ValueError('nothing to compute: no mesh and no positions')
+        if sp_.param and not getattr(self, '_clearance_line', False) and not sp_.rk4:
+            self.problem.clearance_set_line(sp_.line_table())
+            self._clearance_line = True
+        S = int(samples)
+        S1 = sp_.K1 if S == 0 else S + 1
+        opts = {'device': self.device, 'dtype': torch.float64}
+        pos = torch.empty((3, sp_.N, S1, B) if il else (B, sp_.N, S1, 3), **opts) if positions else None
+        dist = torch.empty((sp_.N, S1, B) if il else (B, sp_.N, S1), **opts) if mesh is not None else None
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self.problem.clearance_ptrs(B, W.data_ptr(), S, pos.data_ptr() if positions else 0,
+                                    dist.data_ptr() if mesh is not None else 0,
+                                    mesh.handle if mesh is not None else None,
+                                    cull=int(DEFAULT_CULL if cull is None else bool(cull)), layout=self.layout,
+                                    stream=st.cuda_stream)
+        return pos, dist
+
     def remesh_from(self, src: 'BatchedNLP', W_src, cols=None, stream=None) -> torch.Tensor:
         '''
         Transfer decision vectors of the batch `src` (the same scenario on a coarser mesh: this N a multiple

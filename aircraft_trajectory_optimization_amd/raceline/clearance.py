@@ -1,0 +1,100 @@
+'''
+Clearance of solved racelines from the obstacle mesh on the device.
+
+The replay (raceline/replay.py) says whether a solution flies; this asks the other question the obstacle
+problems raise: does it hit the arena? The obstacle rows of the NLP are spheres at the collocation nodes, and
+the reference's own collision test (base_raceline.py:1312-1327) looks at the nodes only, so nothing constrains
+or checks the polynomial between them. Here every interval is sampled densely (libato's ato_clearance:
+positions of the transcription's own polynomial, lifted through the centreline at each sample's own s, and
+their signed distance to the mesh through the tiled kernel), or, with flown=True, the trajectory the vehicle
+ODE actually flies under the solution's inputs (the replay's dense trajectory) is.
+
+It certifies positions against the mesh. It says nothing about gates, variable bounds or s' >= 0 between the
+nodes, and between two samples only what the chord bound below gives.
+'''
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from aircraft_trajectory_optimization_amd import native
+from aircraft_trajectory_optimization_amd.raceline.batched import BatchedNLP
+from aircraft_trajectory_optimization_amd.raceline.problem import ProblemSpec
+
+
+@dataclass
+class ClearanceResult:
+    ''' device tensors of one clearance audit of B instances; S1 points per interval '''
+    pos: torch.Tensor            # (3, N, S1, B) global positions
+    dist: torch.Tensor           # (N, S1, B) signed distance to the mesh, positive outside
+    d_min: torch.Tensor          # (B,) smallest distance of the instance
+    where: torch.Tensor          # (B, 2) interval and sample of that minimum
+    gap: torch.Tensor            # (B,) longest chord between consecutive samples inside an interval
+    passed: torch.Tensor         # (B,) bool: d_min >= r_c
+    certified: torch.Tensor      # (B,) bool: d_min - gap / 2 >= r_c
+    collision_radius: float = 0.0
+    samples: int = 16
+    flown: bool = False
+
+
+def reduce_clearance(pos: torch.Tensor, dist: torch.Tensor, r_c: float, samples: int, flown: bool) -> ClearanceResult:
+    ''' the per-instance reductions of pos (3, N, S1, B) and dist (N, S1, B): torch ops on their device '''
+    N, S1, B = dist.shape
+    flat = dist.reshape(N * S1, B)
+    d_min, idx = flat.min(dim=0)
+    where = torch.stack([idx // S1, idx % S1], dim=1)
+    if S1 > 1:
+        gap = (pos[:, :, 1:, :] - pos[:, :, :-1, :]).square().sum(dim=0).sqrt().reshape(-1, B).amax(dim=0)
+    else:
+        gap = torch.zeros(B, dtype=dist.dtype, device=dist.device)
+    return ClearanceResult(pos=pos, dist=dist, d_min=d_min, where=where, gap=gap, passed=d_min >= r_c,
+                           certified=d_min - gap / 2 >= r_c, collision_radius=float(r_c), samples=int(samples),
+                           flown=bool(flown))
+
+
+def clearance_solutions(spec: ProblemSpec, X, mesh_obstacle, samples: int = 16,
+                        collision_radius: Optional[float] = None, flown: bool = False,
+                        device: Optional[torch.device] = None, cull: Optional[bool] = None) -> ClearanceResult:
+    '''
+    Audit decision vectors X of the problem `spec` against `mesh_obstacle` (a MeshObstacle): a host array
+    (B, nw) (or one vector (nw,)), or a device tensor (nw, B) as the batched solver returns its x.
+
+    samples = S >= 1: S + 1 points per interval of the collocation polynomial at i / S, both ends; samples = 0:
+    the K + 1 nodes, which is the reference's collision test. flown=True: the S states per interval of
+    replay(substeps=S, trajectory=True) instead, the trajectory the global vehicle ODE flies from every
+    interval's start under the solution's own inputs (the interval's start state itself is not among them;
+    the problems the replay does not cover raise NotImplementedError).
+
+    passed = d_min >= r_c is the reference's verdict on the sampled points (r_c defaults to the vehicle's
+    collision_radius). certified = d_min - gap / 2 >= r_c uses that the distance to the mesh is 1-Lipschitz:
+    a point of the chord between two consecutive samples is within gap / 2 of one of them, so every point of
+    the chord POLYLINE through the samples of an interval is then clear as well. It bounds the polyline, not
+    the polynomial arc (or the flown arc) between the samples, which may bulge away from its chord. With
+    flown=True the polyline starts at the state after the FIRST substep: the first 1 / S of every interval,
+    from its start state to that sample, is covered by neither `passed` nor `certified` (the polynomial audit
+    with the same `samples` covers the start state itself, its sample 0).
+    '''
+    if torch.is_tensor(X):
+        X = X.reshape(X.shape[0], -1).to(torch.float64)
+        B = X.shape[1]
+    else:
+        X = np.atleast_2d(np.asarray(X, np.float64))
+        B = X.shape[0]
+    r_c = float(spec.vehicle.collision_radius if collision_radius is None else collision_radius)
+    nlp = BatchedNLP(spec, B, layout=native.ATO_LAYOUT_INTERLEAVED, device=device, buffers=False)
+    if torch.is_tensor(X):
+        X = X.to(nlp.device)
+    S = int(samples)
+    with torch.cuda.device(nlp.device):
+        if flown:
+            if S < 1:
+                raise ValueError('flown=True needs samples >= 1 (the replay substeps per interval)')
+            traj = nlp.replay(X, substeps=S, trajectory=True)[2]          # (N, S, nz, B)
+            pos = traj[:, :, :3, :].permute(2, 0, 1, 3).contiguous()     # (3, N, S, B)
+            n = spec.N * S * B
+            dist = mesh_obstacle.signed_distance_strided(pos, n, 1, n, **({} if cull is None else {'cull': cull}))
+            dist = dist.reshape(spec.N, S, B)
+        else:
+            pos, dist = nlp.clearance(mesh_obstacle, X, samples=S, cull=cull)
+        return reduce_clearance(pos, dist, r_c, S, flown)

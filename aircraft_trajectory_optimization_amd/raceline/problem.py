@@ -347,6 +347,22 @@ class ProblemSpec:
         tbl[:, 3:] = np.stack([es, ey, en], axis=2).transpose(1, 0, 2).reshape(-1, 9)
         return tbl
 
+    def line_table(self) -> dict:
+        '''
+        Centreline table of the clearance (ato_clearance_set_line): the two piecewise cubics of a
+        SplineCenterline, x_c and r_y, as {'xc_knots' (n,), 'xc_coef' (n + 1, 4, 3), 'ry_knots' (m,), 'ry_coef'
+        (m + 1, 4, 3)}: coefficient [piece, power 0..3, axis], piece 0 left of the first knot and the last piece
+        right of the last knot (linear extrapolation), the piece of s being the number of knots <= s. With
+        these the device evaluates x_c(s) + y e_y(s) + n e_n(s) at any s, as line.p2x does on the host.
+        '''
+        if not self.param:
+            raise ValueError('the centreline table belongs to parametric problems')
+        xc, ry = getattr(self.line, '_xc', None), getattr(self.line, '_ry', None)
+        if xc is None or ry is None:
+            raise NotImplementedError('the centreline table needs a spline centreline (piecewise cubics x_c, r_y)')
+        return {'xc_knots': np.ascontiguousarray(xc.knots, float), 'xc_coef': np.ascontiguousarray(xc.coef, float),
+                'ry_knots': np.ascontiguousarray(ry.knots, float), 'ry_coef': np.ascontiguousarray(ry.coef, float)}
+
     def native_spec(self) -> dict:
         ''' dict consumed by native.DescHolder '''
         v = self.vehicle

@@ -195,6 +195,17 @@ int ato_mesh_destroy(ato_mesh* mesh);
 int ato_mesh_signed_distance(ato_mesh* mesh, int32_t n, const double* points, double* dist, double* closest,
                              void* stream);
 
+/* The same distance for points of any regular layout: component c of point p at
+ * points[p * stride_point + c * stride_comp] (device), dist (device [n]). It walks a second copy of the
+ * triangles, sorted at ato_mesh_create by the Morton code of their centroids and cut into tiles with
+ * axis-aligned boxes; one wave is 64 consecutive points, so it is meant for coherent point sets
+ * (consecutive points close together). cull = 0 visits every tile; cull = 1 skips a tile's distance
+ * pass when no point of the wave can be nearer to its box than the point's best so far, and its
+ * crossing pass when no point's ray meets the box. Both give the distances of ato_mesh_signed_distance.
+ * Asynchronous on stream. */
+int ato_mesh_signed_distance_strided(ato_mesh* mesh, int64_t n, const double* points, int64_t stride_point,
+                                     int64_t stride_comp, double* dist, int32_t cull, void* stream);
+
 /* Replay of collocation solutions through the vehicle ODE (csrc/ato_replay.hpp): per (instance,
  * interval) the start state Z[n,0], lifted to the global model, is integrated over h_n with
  * `substeps` classical RK4 steps under the solution's own inputs u(tau) = sum_j l_j(tau) U[n,j] and
@@ -240,6 +251,31 @@ int ato_replay(ato_handle* h, int32_t batch, int32_t layout, const double* w, in
  * ATO_ERR_UNSUPPORTED: an RK4-transcribed problem, or one that carries CPC progress variables. */
 int ato_remesh(ato_handle* src, ato_handle* dst, int32_t batch_src, int32_t batch_dst, int32_t layout,
                const double* w_src, const int32_t* cols, double* w_dst, void* stream);
+
+/* Clearance of collocation solutions from an obstacle mesh (csrc/ato_clearance.hpp): per (instance, interval,
+ * sample) the global position of the interval's own polynomial, sum_j l_j(x_i) Z[n, j, 0..2], and its signed
+ * distance to the mesh. samples = S in [1, 64]: S + 1 points per interval at x_i = i / S, both ends; samples = 0:
+ * the K + 1 collocation nodes (the reference's collision test, base_raceline.py:1312-1327). S1 is that count.
+ * Parametric problems (global_r or the relative attitude) are placed by x_c(s) + y e_y(s) + n e_n(s) at the
+ * sample's own interpolated s, from the centreline's two piecewise cubics: knots [n] and coefficients
+ * [n + 1][4][3] (piece, power 0..3, axis) of x_c and of r_y, piece 0 left of the first knot and piece n right of
+ * the last (linear extrapolation), the piece of s being the number of knots <= s. Host arrays, copied; not needed
+ * (ignored) for global-frame problems. It certifies positions against the mesh, nothing about gates, bounds or
+ * the arc between samples. */
+typedef struct ato_line_table {
+    int32_t n_xc, n_ry;
+    const double *xc_knots, *xc_coef, *ry_knots, *ry_coef;
+} ato_line_table;
+int ato_clearance_set_line(ato_handle* h, const ato_line_table* line);
+/* w [nw x batch] in `layout`. pos: point p, component c at [c * N*S1*batch + p] with p = (n S1 + i) batch + b
+ * (interleaved) or at [p * 3 + c] with p = (b N + n) S1 + i (instance-major); dist [N*S1*batch] by the same p
+ * (ato_mesh_signed_distance_strided with `cull`). mesh and dist may be NULL: positions only. pos may be NULL
+ * when dist is wanted: a buffer on the handle, grown only when a call needs more. Asynchronous on stream; no
+ * device-wide synchronisation; the weight table is uploaded on the stream when samples changes.
+ * ATO_ERR_UNSUPPORTED: RK4 transcription; ATO_ERR_STATE: a parametric problem without its centreline table;
+ * ATO_ERR_ARG: samples outside [0, 64], batch < 1, unknown layout; nothing is launched or written then. */
+int ato_clearance(ato_handle* h, ato_mesh* mesh, int32_t batch, int32_t layout, const double* w, int32_t samples,
+                  double* pos, double* dist, int32_t cull, void* stream);
 
 /* Per-kernel timing with HIP events recorded on the evaluation stream. ato_timing(h, n)
  * allocates n event slots and starts recording (n = 0 stops); while on, each ato_eval

@@ -1,0 +1,203 @@
+// clearance_hostcheck.cpp -- TEST-ONLY CPU twin of the clearance kernels.
+//
+// Compiles csrc/ato_clearance.hpp and csrc/ato_mesh_pair.hpp with g++ (no HIP) and runs the same
+// clearance_point() the position kernel runs, one (instance, interval, sample) at a time, with the same
+// argument checks and weight table; and the tiled signed distance over "waves" of 64 consecutive points with
+// the kernel's own tiles (build_tiles), pair functions and decision functions (box_lb2, ray_meets_box). It is
+// never loaded by the product package.
+#include <string>
+#include <vector>
+#include "../../aircraft_trajectory_optimization_amd/csrc/ato_layout.hpp"
+#include "../../aircraft_trajectory_optimization_amd/csrc/ato_clearance.hpp"
+#include "../../aircraft_trajectory_optimization_amd/csrc/ato_mesh_pair.hpp"
+
+namespace {
+thread_local std::string last_err;
+}  // namespace
+
+struct atoc_handle {
+    ato::Layout L;
+    std::vector<double> line;
+    ato::LineD ld{};
+};
+
+struct atoc_mesh {
+    int nf = 0, nt = 0;
+    std::vector<double> tri, sorted, boxes;
+};
+
+extern "C" {
+
+const char* atoc_last_error() { return last_err.c_str(); }
+
+int atoc_create(const ato_problem_desc* d, atoc_handle** out) {
+    auto* h = new atoc_handle();
+    std::string e = h->L.build(*d);
+    if (!e.empty()) {
+        last_err = e;
+        delete h;
+        return ATO_ERR_ARG;
+    }
+    *out = h;
+    return ATO_OK;
+}
+
+void atoc_destroy(atoc_handle* h) { delete h; }
+
+int atoc_set_line(atoc_handle* h, const ato_line_table* t) {
+    if (h->L.p.frame == ato::GLOBAL) return ATO_OK;
+    const size_t nx = (size_t)t->n_xc, nr = (size_t)t->n_ry;
+    std::vector<double>& b = h->line;
+    b.clear();
+    b.insert(b.end(), t->xc_knots, t->xc_knots + nx);
+    b.insert(b.end(), t->xc_coef, t->xc_coef + (nx + 1) * 12);
+    b.insert(b.end(), t->ry_knots, t->ry_knots + nr);
+    b.insert(b.end(), t->ry_coef, t->ry_coef + (nr + 1) * 12);
+    const double* d = b.data();
+    h->ld = ato::LineD{t->n_xc, t->n_ry, d, d + nx, d + nx + (nx + 1) * 12, d + nx + (nx + 1) * 12 + nr};
+    return ATO_OK;
+}
+
+// the weight table of ato_clearance for this problem: wt [S1][K + 1]
+void atoc_weights(const atoc_handle* h, int samples, double* wt) {
+    ato::clearance_weights(h->L.p.tau, h->L.p.K1, samples, wt);
+}
+
+// the positions of ato_clearance on host arrays (same layouts, same return codes)
+int atoc_clearance(const atoc_handle* h, int B, int layout, const double* w, int samples, double* pos) {
+    const ato::ProbD& p = h->L.p;
+    const char* msg = "";
+    if (int rc = ato::clearance_check(p, !h->line.empty(), B, layout, samples, &msg)) {
+        last_err = msg;
+        return rc;
+    }
+    const int S1 = ato::clearance_points(p.K1, samples);
+    std::vector<double> wt((size_t)S1 * p.K1);
+    ato::clearance_weights(p.tau, p.K1, samples, wt.data());
+    const ato::ClearD a = ato::clearance_args(p, samples, wt.data(), h->ld);
+    const bool il = layout == ATO_LAYOUT_INTERLEAVED;
+    const long plane = (long)a.N * S1 * B;
+    for (int n = 0; n < a.N; ++n)
+        for (int i = 0; i < S1; ++i)
+            for (int b = 0; b < B; ++b) {
+                double out[3];
+                ato::clearance_point(a, n, i, w + (il ? (long)b : (long)b * a.nw), il ? (long)B : 1L, out);
+                for (int c = 0; c < 3; ++c) {
+                    if (il) pos[c * plane + ((long)n * S1 + i) * B + b] = out[c];
+                    else pos[(((long)b * a.N + n) * S1 + i) * 3 + c] = out[c];
+                }
+            }
+    return ATO_OK;
+}
+
+// the triangles and tiles of ato_mesh_create
+int atoc_mesh_create(const double* vertices, int nv, const int32_t* faces, int nf, atoc_mesh** out) {
+    auto* m = new atoc_mesh();
+    m->nf = nf;
+    m->tri.resize((size_t)nf * 9);
+    for (int f = 0; f < nf; ++f)
+        for (int c = 0; c < 3; ++c) {
+            const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+            if (i0 < 0 || i0 >= nv || i1 < 0 || i1 >= nv || i2 < 0 || i2 >= nv) {
+                delete m;
+                return ATO_ERR_ARG;
+            }
+            const double a = vertices[3 * i0 + c];
+            m->tri[(size_t)f * 9 + c] = a;
+            m->tri[(size_t)f * 9 + 3 + c] = vertices[3 * i1 + c] - a;
+            m->tri[(size_t)f * 9 + 6 + c] = vertices[3 * i2 + c] - a;
+        }
+    ato_mesh_pair::build_tiles(m->tri, nf, m->sorted, m->boxes);
+    m->nt = ato_mesh_pair::mesh_tiles(nf);
+    *out = m;
+    return ATO_OK;
+}
+
+void atoc_mesh_destroy(atoc_mesh* m) { delete m; }
+
+int atoc_mesh_tiles(const atoc_mesh* m) { return m->nt; }
+
+// k_mesh_sdist on host arrays: every point against every triangle in face order
+void atoc_mesh_sdist(const atoc_mesh* m, long n, const double* pts, double* dist) {
+    using namespace ato_mesh_pair;
+    for (long i = 0; i < n; ++i) {
+        const V3 p = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+        double best = 1e300;
+        int crossings = 0;
+        for (int f = 0; f < m->nf; ++f) {
+            const double* q = &m->tri[(size_t)f * 9];
+            const double d2 = pair_dist2(p, q);
+            if (d2 < best) best = d2;
+            crossings += pair_ray(p, q) ? 1 : 0;
+        }
+        const double d = sqrt(best);
+        dist[i] = (crossings & 1) ? -d : d;
+    }
+}
+
+// k_mesh_sdist_tiles on host arrays, wave by wave. counts[0..2]: (wave, tile) pairs in all, those whose
+// distance pass was skipped, those whose crossing pass was skipped.
+void atoc_mesh_sdist_strided(const atoc_mesh* m, long n, const double* pts, long sp, long sc, double* dist, int cull,
+                             long* counts) {
+    using namespace ato_mesh_pair;
+    const double *tri = m->sorted.data(), *boxes = m->boxes.data();
+    const int nf = m->nf, nt = m->nt;
+    counts[0] = counts[1] = counts[2] = 0;
+    for (long i0 = 0; i0 < n; i0 += 64) {
+        V3 p[64];
+        double best[64];
+        int crossings[64];
+        for (int l = 0; l < 64; ++l) {
+            const long ii = i0 + l < n ? i0 + l : n - 1;
+            p[l] = V3{pts[ii * sp], pts[ii * sp + sc], pts[ii * sp + 2 * sc]};
+            best[l] = 1e300;
+            crossings[l] = 0;
+        }
+        int seed = -1;
+        if (cull) {
+            double lb0 = box_lb2(p[0], boxes);
+            seed = 0;
+            for (int t = 1; t < nt; ++t) {
+                const double lb = box_lb2(p[0], boxes + (long)t * 6);
+                if (lb < lb0) {
+                    lb0 = lb;
+                    seed = t;
+                }
+            }
+            const int cnt = std::min(MESH_TILE, nf - seed * MESH_TILE);
+            for (int k = 0; k < cnt; ++k)
+                for (int l = 0; l < 64; ++l)
+                    best[l] = fmin(best[l], pair_dist2(p[l], tri + ((long)seed * MESH_TILE + k) * 9));
+        }
+        for (int t = 0; t < nt; ++t) {
+            bool nd = true, nr = true;
+            if (cull) {
+                const double* bx = boxes + (long)t * 6;
+                nd = nr = false;
+                for (int l = 0; l < 64; ++l) {
+                    nd = nd || box_lb2(p[l], bx) < best[l];
+                    nr = nr || ray_meets_box(p[l], bx);
+                }
+                nd = nd && t != seed;
+            }
+            counts[0] += 1;
+            counts[1] += (!nd && t != seed) ? 1 : 0;
+            counts[2] += nr ? 0 : 1;
+            if (!nd && !nr) continue;
+            const int cnt = std::min(MESH_TILE, nf - t * MESH_TILE);
+            for (int k = 0; k < cnt; ++k) {
+                const double* q = tri + ((long)t * MESH_TILE + k) * 9;
+                for (int l = 0; l < 64; ++l) {
+                    if (nd) best[l] = fmin(best[l], pair_dist2(p[l], q));
+                    if (nr) crossings[l] += pair_ray(p[l], q) ? 1 : 0;
+                }
+            }
+        }
+        for (int l = 0; l < 64 && i0 + l < n; ++l) {
+            const double d = sqrt(best[l]);
+            dist[i0 + l] = (crossings[l] & 1) ? -d : d;
+        }
+    }
+}
+
+}  // extern "C"

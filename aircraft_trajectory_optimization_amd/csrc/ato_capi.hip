@@ -60,6 +60,7 @@ static void release(ato_handle* h) {
     (void)hipFree(h->d_line);
     (void)hipFree(h->d_clear_w);
     (void)hipFree(h->d_clear_pos);
+    (void)hipFree(h->d_audit_w);
     h->remesh_tabs.clear();
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
     h->events.clear();
@@ -145,6 +146,13 @@ static int create_impl(const ato_problem_desc* desc, ato_handle** out) {
         release(h);
         delete h;
         return fail(ATO_ERR_HIP, "clearance weight table: out of device memory");
+    }
+    // the audit's two weight tables likewise
+    if (hipMalloc((void**)&h->d_audit_w, (size_t)2 * (ato::CLEAR_SMAX + 1) * (ATO_KMAX + 1) * sizeof(double)) !=
+        hipSuccess) {
+        release(h);
+        delete h;
+        return fail(ATO_ERR_HIP, "audit weight tables: out of device memory");
     }
     h->pd = h->L.p;
     h->pd.geom = h->d_geom;
@@ -582,6 +590,40 @@ static int clearance_impl(ato_handle* h, ato_mesh* mesh, int32_t batch, int32_t 
 extern "C" int ato_clearance(ato_handle* h, ato_mesh* mesh, int32_t batch, int32_t layout, const double* w,
                              int32_t samples, double* pos, double* dist, int32_t cull, void* stream) {
     ATO_NOEXCEPT_BODY(clearance_impl(h, mesh, batch, layout, w, samples, pos, dist, cull, stream))
+}
+
+static int audit_impl(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t samples,
+                      const double* lb, const double* ub, int32_t bounds_per_instance, double* val, void* stream) {
+    if (!h) return fail(ATO_ERR_ARG, "null handle");
+    const ato::ProbD& p = h->pd;
+    const char* msg = "";
+    if (int rc = ato::audit_check(p, h->d_line != nullptr, batch, layout, samples, lb != nullptr, ub != nullptr, &msg))
+        return fail(rc, msg);
+    if (!w || !val) return fail(ATO_ERR_ARG, "null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    const int S1 = ato::clearance_points(p.K1, samples);
+    const size_t len = (size_t)S1 * p.K1;
+    if (h->audit_samples != samples) {
+        std::vector<double>& tab = h->audit_w_host[samples];
+        if (tab.empty()) {
+            tab.resize(2 * len);
+            ato::clearance_weights(p.tau, p.K1, samples, tab.data());
+            ato::audit_dweights(p.tau, p.C, p.K1, samples, tab.data() + len);
+        }
+        ATO_HIP(hipMemcpyAsync(h->d_audit_w, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        h->audit_samples = samples;
+    }
+    const ato::AuditD a =
+        ato::audit_args(p, samples, h->d_audit_w, h->d_audit_w + len, h->line, lb, ub, bounds_per_instance);
+    hipError_t e = hipErrorInvalidValue;
+    ato::with_model(p, [&]<class M>() { e = ato::launch_audit<M>(a, batch, layout, w, val, st); });
+    if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("audit launch: ") + hipGetErrorString(e));
+    return ATO_OK;
+}
+
+extern "C" int ato_audit(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t samples,
+                         const double* lb, const double* ub, int32_t bounds_per_instance, double* val, void* stream) {
+    ATO_NOEXCEPT_BODY(audit_impl(h, batch, layout, w, samples, lb, ub, bounds_per_instance, val, stream))
 }
 
 extern "C" int ato_eval(ato_handle* h, int32_t batch, int32_t layout, const double* w, double* g,

@@ -9,7 +9,8 @@
 // does not depend on the attitude) q = (s, y, n) and the position is
 //   x_c(s) + y e_y(s) + n e_n(s)
 // with the centreline evaluated at the sample's own interpolated s: s is free at interior nodes, so a
-// per-boundary table (the replay's) does not reach them. The centreline is the two piecewise cubics of
+// per-boundary table (the replay's) does not reach them. (Bounds, s' >= 0 and the ODE defects at the same samples:
+// ato_audit.hpp.) The centreline is the two piecewise cubics of
 // SplineCenterline (_xc and _ry, linear extrapolation pieces included; piece = number of knots <= s) and
 // the frame is frame_from_terms: e_s = x_c' / |x_c'|, e_y = normalise(r_y - e_s (e_s . r_y)),
 // e_n = e_s x e_y. CPC variables sit after the node block and are not read.

@@ -7,6 +7,7 @@
 #include "ato_replay.hpp"
 #include "ato_remesh.hpp"
 #include "ato_clearance.hpp"
+#include "ato_audit.hpp"
 
 struct ato_handle {
     ato::Layout L;
@@ -76,4 +77,9 @@ struct ato_handle {
     std::map<int32_t, std::vector<double>> clear_w_host;
     double* d_clear_pos = nullptr;
     size_t clear_pos_len = 0;
+    // audit (ato_audit.hpp): value and derivative weight tables of the sample count last used, back to back
+    // in one allocation sized for CLEAR_SMAX, uploaded from per-count host tables that are never rewritten
+    double* d_audit_w = nullptr;
+    int32_t audit_samples = -1;
+    std::map<int32_t, std::vector<double>> audit_w_host;
 };

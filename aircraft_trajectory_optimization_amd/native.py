@@ -19,6 +19,7 @@ ATO_FRAME_GLOBAL, ATO_FRAME_PARAMETRIC = 0, 1
 ATO_TRANS_COLLOCATION, ATO_TRANS_RK4 = 0, 1
 ATO_GATE_CIRCLE, ATO_GATE_SQUARE = 0, 1
 ATO_LAYOUT_INTERLEAVED, ATO_LAYOUT_INSTANCE_MAJOR = 0, 1
+ATO_AUDIT_NCH = 14      # channels per item of ato_audit
 ATO_OK, ATO_ERR_ARG, ATO_ERR_UNSUPPORTED, ATO_ERR_HIP, ATO_ERR_STATE = 0, -1, -2, -3, -4
 ABI_VERSION = 3
 CPC_MAX = 16                 # ATO_CPC_MAX
@@ -135,7 +136,7 @@ EXPORTED_SYMBOLS = ('ato_create', 'ato_destroy', 'ato_sizes', 'ato_sparsity', 'a
                     'ato_kkt_residual', 'ato_kkt_residual_list', 'ato_set_instance_spheres',
                     'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity', 'ato_replay_set_lift',
                     'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided', 'ato_clearance_set_line',
-                    'ato_clearance') + IPM_SYMBOLS
+                    'ato_clearance', 'ato_audit') + IPM_SYMBOLS
 
 
 def library_path() -> str:
@@ -179,6 +180,7 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
         lib.ato_clearance_set_line.argtypes = [vp, ctypes.POINTER(AtoLineTable)]
         lib.ato_clearance.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp,
                                       ctypes.c_int32, vp]
+        lib.ato_audit.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp]
         lib.ato_kkt_create.argtypes = [vp, ctypes.POINTER(vp)]
         lib.ato_kkt_destroy.argtypes = [vp]
         lib.ato_kkt_reserve.argtypes = [vp, ctypes.c_int32]
@@ -224,7 +226,7 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
                    'ato_timing_read', 'ato_timing_stride', 'ato_mesh_create', 'ato_mesh_destroy', 'ato_mesh_signed_distance',
                    'ato_set_instance_spheres', 'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity',
                    'ato_replay_set_lift', 'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided',
-                   'ato_clearance_set_line', 'ato_clearance'):
+                   'ato_clearance_set_line', 'ato_clearance', 'ato_audit'):
             getattr(lib, fn).restype = ctypes.c_int
     return lib
 
@@ -492,6 +494,26 @@ class NativeProblem:
         library's message.
         '''
         rc = self.clearance_rc(batch, w, samples, pos, dist, mesh, cull, layout, stream)
+        if rc == ATO_ERR_UNSUPPORTED:
+            raise NotImplementedError(self.lib.ato_last_error().decode())
+        self._check(rc)
+
+    def audit_rc(self, batch: int, w: int, samples: int, val: int, lb: int = 0, ub: int = 0,
+                 bounds_per_instance: bool = False, layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0) -> int:
+        ''' ato_audit on device pointers; returns the library's code (ato_last_error has the message) '''
+        return self.lib.ato_audit(self.handle, int(batch), int(layout), w or None, int(samples), lb or None,
+                                  ub or None, int(bool(bounds_per_instance)), val or None, stream or None)
+
+    def audit_ptrs(self, batch: int, w: int, samples: int, val: int, lb: int = 0, ub: int = 0,
+                   bounds_per_instance: bool = False, layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0):
+        '''
+        Audit of the decision vectors w between their nodes (asynchronous on `stream`; include/ato.h ato_audit):
+        S1 = samples + 1 points per interval (samples = 0: the K + 1 nodes), val [ATO_AUDIT_NCH x N S1 batch]
+        (interleaved) or [N S1 batch x ATO_AUDIT_NCH]; lb, ub: bounds per component of the node vector [NV], or
+        [NV x batch] in the layout with bounds_per_instance; both 0: no bounds. RK4-transcribed problems raise
+        NotImplementedError with the library's message.
+        '''
+        rc = self.audit_rc(batch, w, samples, val, lb, ub, bounds_per_instance, layout, stream)
         if rc == ATO_ERR_UNSUPPORTED:
             raise NotImplementedError(self.lib.ato_last_error().decode())
         self._check(rc)

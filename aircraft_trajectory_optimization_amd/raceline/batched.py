@@ -207,6 +207,58 @@ class BatchedNLP:
                                     stream=st.cuda_stream)
         return pos, dist
 
+    def audit(self, W=None, samples: int = 16, lb=None, ub=None, stream=None) -> torch.Tensor:
+        '''
+        Everything the NLP constrains at a node, evaluated at S1 points of every interval (ato_audit,
+        asynchronous on `stream`): S1 = samples + 1 points of the collocation polynomial at i / samples
+        (samples = 0: the K + 1 nodes), parametric problems with the geometry at the sample's own s. W as in
+        replay(). lb, ub: bounds per component of the node vector (raceline.audit.path_bounds), (NV,) shared or
+        (B, NV) per instance, host arrays or device tensors; None: no bounds (+inf in channels 0-5). Returns
+        val in the layout: interleaved (NCH, N, S1, B), instance-major (B, N, S1, NCH); the channels are listed
+        in include/ato.h. One stream per problem handle: the weight tables are handle state. RK4-transcribed
+        problems raise NotImplementedError.
+        '''
+        sp_, B = self.spec, self.batch
+        il = self.layout == native.ATO_LAYOUT_INTERLEAVED
+        if W is None:
+            if self.w is None or self.fp32:
+                raise TypeError('audit needs fp64 decision vectors (pass W)')
+            W = self.w
+        elif not torch.is_tensor(W):
+            t = torch.as_tensor(np.array(W, np.float64).reshape(B, -1))
+            W = (t.T.contiguous() if il else t.contiguous()).to(self.device)
+        if W.dtype != torch.float64 or tuple(W.shape) != ((self.problem.nw, B) if il else (B, self.problem.nw)):
+            raise ValueError('W must be fp64 in the layout of this batch')
+        W = W.contiguous()
+        if (lb is None) != (ub is None):
+            raise ValueError('lb and ub must both be given or both be None')
+        per = False
+        if lb is not None:
+            lb, ub = ((v.to(torch.float64) if torch.is_tensor(v) else torch.as_tensor(np.array(v, np.float64)))
+                      .to(self.device) for v in (lb, ub))
+            if lb.shape != ub.shape or tuple(lb.shape) not in ((sp_.nv,), (B, sp_.nv)):
+                raise ValueError(f'lb and ub must both be ({sp_.nv},) or ({B}, {sp_.nv})')
+            per = lb.dim() == 2
+            if per and il:
+                lb, ub = lb.T, ub.T
+            lb, ub = lb.contiguous(), ub.contiguous()
+        if sp_.param and not getattr(self, '_clearance_line', False) and not sp_.rk4:
+            self.problem.clearance_set_line(sp_.line_table())
+            self._clearance_line = True
+        S = int(samples)
+        S1 = sp_.K1 if S == 0 else S + 1
+        nch = native.ATO_AUDIT_NCH
+        val = torch.empty((nch, sp_.N, S1, B) if il else (B, sp_.N, S1, nch), device=self.device, dtype=torch.float64)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if stream is not None:      # temporaries made on the current stream, read on another
+            for t in (W, lb, ub):
+                if t is not None:
+                    t.record_stream(st)
+        self.problem.audit_ptrs(B, W.data_ptr(), S, val.data_ptr(), lb.data_ptr() if lb is not None else 0,
+                                ub.data_ptr() if ub is not None else 0, per, layout=self.layout,
+                                stream=st.cuda_stream)
+        return val
+
     def remesh_from(self, src: 'BatchedNLP', W_src, cols=None, stream=None) -> torch.Tensor:
         '''
         Transfer decision vectors of the batch `src` (the same scenario on a coarser mesh: this N a multiple

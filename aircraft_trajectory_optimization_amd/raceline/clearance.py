@@ -9,8 +9,9 @@ positions of the transcription's own polynomial, lifted through the centreline a
 their signed distance to the mesh through the tiled kernel), or, with flown=True, the trajectory the vehicle
 ODE actually flies under the solution's inputs (the replay's dense trajectory) is.
 
-It certifies positions against the mesh. It says nothing about gates, variable bounds or s' >= 0 between the
-nodes, and between two samples only what the chord bound below gives.
+It certifies positions against the mesh. Variable bounds, s' >= 0 and the ODE defects between the nodes are the
+audit's (raceline/audit.py); nothing checks gates there, and between two samples only the chord bound below
+holds.
 '''
 from dataclasses import dataclass
 from typing import Optional

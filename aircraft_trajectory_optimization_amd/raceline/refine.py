@@ -26,9 +26,9 @@ from aircraft_trajectory_optimization_amd.raceline.replay import ReplayResult, r
 class RefineResult:
     ''' one refinement of B instances, of which the columns `cols` were re-solved on the finer mesh '''
     spec: ProblemSpec                      # the destination problem
-    cols: np.ndarray                       # selected source columns (ascending)
-    before: ReplayResult                   # replay of every source column (None with select='all' where the
-                                           # replay does not cover the problem)
+    cols: np.ndarray                       # selected source columns (ascending; an explicit array: as passed)
+    before: ReplayResult                   # replay of every source column (None where the replay does not cover
+                                           # the problem and the selection did not need it)
     x0: Optional[torch.Tensor] = None      # (nw', len(cols)) transferred start of the re-solve
     x: Optional[torch.Tensor] = None       # (nw', len(cols)) re-solved decision vectors
     status: Optional[List[str]] = None
@@ -100,7 +100,7 @@ def transfer_solutions(src_spec: ProblemSpec, X, dst_spec: ProblemSpec, cols=Non
         return dst.remesh_from(src, _as_device(X, src_spec.nw, src.device), cols=cols)
 
 
-def refine_solutions(spec: ProblemSpec, X, factor: int = 2, K: Optional[int] = None, select: str = 'replay',
+def refine_solutions(spec: ProblemSpec, X, factor: int = 2, K: Optional[int] = None, select='replay',
                      pos_tol: Optional[float] = None, options=None, substeps: int = 16,
                      device: Optional[torch.device] = None) -> RefineResult:
     '''
@@ -108,13 +108,22 @@ def refine_solutions(spec: ProblemSpec, X, factor: int = 2, K: Optional[int] = N
     refined_spec(spec, factor, K), warm-solve them there with the batched device solver, and replay the
     result. select='replay': the columns whose replayed position error exceeds pos_tol (m) or is not
     finite; select='all': every column (the only choice for problems the replay does not cover, which
-    with 'replay' raise the replay's own NotImplementedError). The warm solve bounds h to
+    with 'replay' raise the replay's own NotImplementedError); an integer array of columns or a boolean
+    mask over the B columns: those columns, as an audit or a clearance picked them (audit_solutions(...).passed,
+    clearance_solutions(...).passed; host arrays or tensors) -- the replay is then only reported, and `before`
+    is None where the replay does not cover the problem. The warm solve bounds h to
     [h' / 100, 10 h'] around the transferred step sizes (the warm-start convention of drone_guess); every
     other bound is the refined problem's own. options: IPMOptions of the re-solve. If nothing is
     selected, nothing is transferred or solved (x, status and after stay None).
     '''
-    if select not in ('replay', 'all'):
-        raise ValueError("select must be 'replay' or 'all'")
+    explicit = None
+    if not isinstance(select, str):
+        explicit = select.detach().cpu().numpy() if torch.is_tensor(select) else np.asarray(select)
+        if explicit.ndim != 1 or not (explicit.dtype == bool or np.issubdtype(explicit.dtype, np.integer)):
+            raise ValueError('select: a one-dimensional integer array of columns or a boolean mask')
+        select = 'columns'
+    elif select not in ('replay', 'all'):
+        raise ValueError("select must be 'replay', 'all', an integer array of columns or a boolean mask")
     if select == 'replay' and pos_tol is None:
         raise ValueError("select='replay' needs pos_tol (m)")
     dst_spec = refined_spec(spec, factor, K)
@@ -131,6 +140,15 @@ def refine_solutions(spec: ProblemSpec, X, factor: int = 2, K: Optional[int] = N
     B = X.reshape(X.shape[0], -1).shape[1] if torch.is_tensor(X) else np.atleast_2d(np.asarray(X)).shape[0]
     if select == 'all':
         cols = np.arange(B)
+    elif select == 'columns':
+        if explicit.dtype == bool:
+            if explicit.shape[0] != B:
+                raise ValueError(f'select: a mask of {explicit.shape[0]} entries for {B} columns')
+            cols = np.flatnonzero(explicit)
+        else:
+            cols = explicit.astype(np.int64)
+            if len(cols) and (cols.min() < 0 or cols.max() >= B):
+                raise ValueError(f'select: columns outside [0, {B})')
     else:
         bad = ~(before.pos_err <= float(pos_tol))           # exceeds the tolerance, or is not finite
         cols = np.flatnonzero(bad.cpu().numpy())

@@ -260,8 +260,8 @@ int ato_remesh(ato_handle* src, ato_handle* dst, int32_t batch_src, int32_t batc
  * sample's own interpolated s, from the centreline's two piecewise cubics: knots [n] and coefficients
  * [n + 1][4][3] (piece, power 0..3, axis) of x_c and of r_y, piece 0 left of the first knot and piece n right of
  * the last (linear extrapolation), the piece of s being the number of knots <= s. Host arrays, copied; not needed
- * (ignored) for global-frame problems. It certifies positions against the mesh, nothing about gates, bounds or
- * the arc between samples. */
+ * (ignored) for global-frame problems. It certifies positions against the mesh, nothing about gates or the arc
+ * between samples; variable bounds and s' >= 0 between the nodes are ato_audit's. */
 typedef struct ato_line_table {
     int32_t n_xc, n_ry;
     const double *xc_knots, *xc_coef, *ry_knots, *ry_coef;
@@ -276,6 +276,36 @@ int ato_clearance_set_line(ato_handle* h, const ato_line_table* line);
  * ATO_ERR_ARG: samples outside [0, 64], batch < 1, unknown layout; nothing is launched or written then. */
 int ato_clearance(ato_handle* h, ato_mesh* mesh, int32_t batch, int32_t layout, const double* w, int32_t samples,
                   double* pos, double* dist, int32_t cull, void* stream);
+
+/* Audit of collocation solutions between their nodes (csrc/ato_audit.hpp): per (instance, interval, sample), with
+ * the samples of ato_clearance, the whole node vector (z, u, du) of the interval's own polynomial and its state
+ * derivative are evaluated and held against everything the NLP constrains at a node. Channels, ATO_AUDIT_NCH
+ * doubles per item; margins are ">= 0 means satisfied" and +inf where the quantity does not exist, defects are
+ * >= 0 and 0 where the group does not exist:
+ *   0-5   min(v - lb, ub - v) over position / attitude / velocity / body rates / inputs / input rates
+ *   6     s-dot (parametric)
+ *   7     gamma - (k_n y - k_y n) (parametric): with force_regularity (the configuration's default) at EVERY
+ *         sample, although the NLP then carries the row only at nodes whose nominal curvature has
+ *         k_y^2 + k_n^2 > 0.1, so a failed channel 7 may be a constraint the solve never had; without
+ *         force_regularity only where k_y^2 + k_n^2 > 0.1 at the sample's own s, +inf elsewhere
+ *   8     1 - u.u / T_max^2 (point mass)
+ *   9-12  max |f_i(z, u) - z'_i| over the position / attitude / velocity / body-rate rows of the problem's own
+ *         model variant, parametric geometry taken at the sample's own s (table of ato_clearance_set_line)
+ *   13    |q.q - 1| (quaternion), Frobenius norm of R^T R - I (DCM), else 0
+ * lb, ub: device bounds per component of the node vector, [NV], or with bounds_per_instance [NV x batch] in
+ * `layout`; both NULL: +inf in channels 0-5. val: item p, channel c at [c * N*S1*batch + p] with
+ * p = (n S1 + i) batch + b (interleaved) or at [p * ATO_AUDIT_NCH + c] with p = (b N + n) S1 + i
+ * (instance-major). Not covered: obstacle-tube sphere rows, gates and closure rows, CPC variables, the dU rows,
+ * RK4 transcriptions, and the arc between two samples. Asynchronous on stream; no device-wide synchronisation;
+ * both weight tables are uploaded on the stream when samples changes. The tables are per-handle state: use ONE
+ * stream per handle for ato_audit (and likewise for ato_clearance and ato_replay), or synchronise between calls
+ * on different streams: a call on another stream does not wait for an upload queued on the first, and a call with
+ * another sample count overwrites the table a kernel of the first may still read. ATO_ERR_UNSUPPORTED: RK4 transcription;
+ * ATO_ERR_STATE: a parametric problem without its centreline table; ATO_ERR_ARG: samples outside [0, 64],
+ * batch < 1, unknown layout, exactly one of lb / ub NULL; nothing is launched or written then. */
+#define ATO_AUDIT_NCH 14
+int ato_audit(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t samples, const double* lb,
+              const double* ub, int32_t bounds_per_instance, double* val, void* stream);
 
 /* Per-kernel timing with HIP events recorded on the evaluation stream. ato_timing(h, n)
  * allocates n event slots and starts recording (n = 0 stops); while on, each ato_eval

@@ -1,0 +1,313 @@
+'''
+Audit test fixtures: the CPU twin of the audit kernel (tests/native/audit_hostcheck.cpp), the cases the CPU and
+the GPU tests share (those of the clearance tests), their inputs, bounds and the hand-built between-node cases.
+'''
+import ctypes
+import functools
+import os
+import subprocess
+
+import numpy as np
+
+from aircraft_trajectory_optimization_amd import native
+from aircraft_trajectory_optimization_amd.raceline.audit import path_bounds
+from tests import audit_oracle
+from tests.clearance_helpers import CASES, IL, IM, SAMPLES, case_id, case_inputs, case_spec, n_points, node_s_view  # noqa: F401
+from tests.helpers import REPO
+from tests.replay_helpers import replay_inputs
+
+AUDIT_SRC = os.path.join(REPO, 'tests', 'native', 'audit_hostcheck.cpp')
+AUDIT_LIB = os.path.join(REPO, 'tests', 'native', 'libato_auditcheck.so')
+
+NCH = 14
+MARGIN_CH, DEFECT_CH = slice(0, 9), slice(9, 14)
+
+# Twin / device against the numpy oracle (tests/audit_oracle.py), relative to max(1, |value|), over every case of
+# CASES with its three input sets, both layouts, samples 0, 1, 5 and both kinds of bounds (the largest there:
+# margins 2.6554e-13 at obstacles-esp-parametric-K9, defects 5.4383e-14 at obstacles-point-relative-K9), and over
+# the B = 65 / 130 inputs of WAVE_CASES at samples 0 and 5, where more columns reach further into the same
+# rounding. Measured once on the CPU twin (tests/test_audit_cpu.py prints the figures); each bound is 10 x the
+# measured value.
+# Margins (channels 0-8): the largest at MARGIN_CASE.
+MARGIN_MEASURED = 3.7378e-12
+MARGIN_CASE = 'obstacles-dcm-relative-K9, B = 65, samples 0 (channel 6: s\' through the K = 9 derivative weights)'
+MARGIN_TOL = 10 * MARGIN_MEASURED
+# Defects and the attitude deviation (channels 9-13): K = 9 derivative weights (up to ~1e3) over h ~ 0.05 and the
+# curvature divisions amplify rounding. The largest at DEFECT_CASE.
+DEFECT_MEASURED = 1.3422e-13
+DEFECT_CASE = 'obstacles-dcm-relative-K9, B = 65, samples 0'
+DEFECT_TOL = 10 * DEFECT_MEASURED
+# Node audit (samples = 0, every node's s at spec.node_s) against g of the CPU build of the programs: device-formula
+# geometry against the host table's, z' by division against the programs' multiplication by 1 / h.
+# Measured once on the CPU twin over the race-track cases: the largest at race-esp-parametric-K9.
+NODE_MEASURED = 1.1939e-15
+NODE_TOL = 10 * NODE_MEASURED
+
+# The two weight tables of the twin against the oracle's: measured 0 (the same products in the same order, and g++
+# contracts nothing here), so they are asserted equal. One finite bound against a plain numpy margin of the oracle's
+# interpolant, relative to max(1, |value|), over the race-track cases at samples 5: measured 2.2204e-15
+# (race-ypr-global-K2); asserted at 10 x.
+ONE_BOUND_MEASURED = 2.2204e-15
+ONE_BOUND_TOL = 10 * ONE_BOUND_MEASURED
+
+WAVE_CASES = [('race', 'point', 'parametric', 2), ('obstacles', 'dcm', 'relative', 9), ('race', 'esp', 'global', 1)]
+
+SEG_SDOT, SEG_ODE_A, SEG_ODE_B, SEG_REG, SEG_STAGE = 0, 1, 2, 4, 5      # ato::SegKind
+
+
+def build_auditcheck(force=False):
+    ''' the twin, with the g++ line of helpers.build_hostcheck '''
+    csrc = os.path.join(REPO, 'aircraft_trajectory_optimization_amd', 'csrc')
+    srcs = [AUDIT_SRC] + [os.path.join(csrc, f) for f in ('ato_models.hpp', 'ato_dual.hpp', 'ato_program.hpp',
+                                                         'ato_layout.hpp', 'ato_clearance.hpp', 'ato_audit.hpp')]
+    if not force and os.path.exists(AUDIT_LIB) and \
+            os.path.getmtime(AUDIT_LIB) >= max(os.path.getmtime(s) for s in srcs):
+        return AUDIT_LIB
+    subprocess.check_call(['g++', '-std=c++20', '-O3', '-march=x86-64-v3', '-fopenmp', '-fPIC', '-shared', '-o',
+                           AUDIT_LIB, AUDIT_SRC])
+    return AUDIT_LIB
+
+
+@functools.lru_cache(maxsize=None)
+def _lib():
+    lib = ctypes.CDLL(build_auditcheck())
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.atoa_create.argtypes = [ctypes.POINTER(native.AtoProblemDesc), ctypes.POINTER(vp)]
+    lib.atoa_last_error.restype = ctypes.c_char_p
+    lib.atoa_destroy.argtypes = [vp]
+    lib.atoa_set_line.argtypes = [vp, ctypes.POINTER(native.AtoLineTable)]
+    lib.atoa_weights.argtypes = [vp, ci, vp, vp]
+    lib.atoa_seg_rows.argtypes = [vp, ci, vp]
+    lib.atoa_geom.argtypes = [vp, ci, vp, vp]
+    lib.atoa_audit.argtypes = [vp, ci, ci, vp, ci, vp, vp, ci, vp]
+    return lib
+
+
+class AuditTwin:
+    ''' ato_audit on host arrays (CPU build of csrc/ato_audit.hpp) '''
+
+    def __init__(self, spec, set_line=True):
+        self.lib, self.spec = _lib(), spec
+        self.holder = native.DescHolder(spec.native_spec())
+        h = ctypes.c_void_p()
+        if self.lib.atoa_create(ctypes.byref(self.holder.desc), ctypes.byref(h)) != 0:
+            raise RuntimeError(self.lib.atoa_last_error().decode())
+        self.h = h
+        if set_line and spec.param and not spec.rk4:
+            t, self._keep = native.line_table_struct(spec.line_table())
+            self.lib.atoa_set_line(self.h, ctypes.byref(t))
+
+    def __del__(self):
+        try:
+            self.lib.atoa_destroy(self.h)
+        except Exception:  # pylint: disable=broad-except
+            pass
+
+    def last_error(self):
+        return self.lib.atoa_last_error().decode()
+
+    def weights(self, samples):
+        S1 = n_points(self.spec, samples)
+        wt, dw = np.zeros((S1, self.spec.K1)), np.zeros((S1, self.spec.K1))
+        self.lib.atoa_weights(self.h, samples, wt.ctypes.data, dw.ctypes.data)
+        return wt, dw
+
+    def seg_rows(self, kind):
+        ''' first row in g of every node's segment of `kind`, (N, K1); -1: none '''
+        rows = np.zeros(self.spec.P, np.int32)
+        self.lib.atoa_seg_rows(self.h, kind, rows.ctypes.data)
+        return rows.reshape(self.spec.N, self.spec.K1)
+
+    def geom(self, s):
+        s = np.ascontiguousarray(s, np.float64).reshape(-1)
+        out = np.zeros((len(s), 13))
+        self.lib.atoa_geom(self.h, len(s), s.ctypes.data, out.ctypes.data)
+        return out
+
+    def raw(self, W, samples, lb=None, ub=None, layout=IL, batch=None, fill=0.0):
+        '''
+        W (B, nw), lb / ub (NV,) or (B, NV) or None -> (rc, val in the library's own layout: (NCH, N, S1, B)
+        interleaved, (B, N, S1, NCH) instance-major), the output starting from `fill`. batch: the batch argument
+        where it shall differ.
+        '''
+        sp_ = self.spec
+        W = np.ascontiguousarray(np.atleast_2d(W), np.float64)
+        B = W.shape[0]
+        il = layout == IL
+        S1 = n_points(sp_, min(max(int(samples), 0), 64))
+        val = np.full((NCH, sp_.N, S1, B) if il else (B, sp_.N, S1, NCH), fill)
+        win = np.ascontiguousarray(W.T) if il else W
+        per, keep = 0, []
+        for v in (lb, ub):
+            if v is None:
+                keep.append(None)
+                continue
+            v = np.asarray(v, np.float64)
+            per = int(v.ndim == 2)
+            keep.append(np.ascontiguousarray(v.T if (per and il) else v))
+        rc = self.lib.atoa_audit(self.h, B if batch is None else batch, layout, win.ctypes.data, int(samples),
+                                 None if keep[0] is None else keep[0].ctypes.data,
+                                 None if keep[1] is None else keep[1].ctypes.data, per, val.ctypes.data)
+        return rc, val
+
+    def audit(self, W, samples, lb=None, ub=None, layout=IL):
+        ''' W (B, nw) -> (NCH, N, S1, B) '''
+        rc, val = self.raw(W, samples, lb, ub, layout)
+        if rc != 0:
+            raise RuntimeError(f'twin audit error {rc}: {self.last_error()}')
+        return val if layout == IL else np.ascontiguousarray(np.moveaxis(val, (0, 3), (3, 0)))
+
+
+def to_canonical(val, layout):
+    ''' the library's layout -> (NCH, N, S1, B) '''
+    return val if layout == IL else np.ascontiguousarray(np.moveaxis(val, (0, 3), (3, 0)))
+
+
+# parametric cases without force_regularity: channel 7 then exists only where k_y^2 + k_n^2 > 0.1 at the sample
+NOREG_CASES = [(t, m, f, 2) for t in ('race', 'obstacles') for m in ('point', 'esp') for f in ('parametric', 'relative')]
+
+
+@functools.lru_cache(maxsize=None)
+def noreg_spec(track, model, frame, K):
+    ''' the case's problem with config.force_regularity = False (same variables: the case's inputs fit) '''
+    from aircraft_trajectory_optimization_amd.raceline.problem import ProblemSpec
+    base = case_spec(track, model, frame, K)
+    cfg = base.config.copy()
+    cfg.force_regularity = False
+    spec = ProblemSpec(base.line, cfg, base.vehicle, base.frame)
+    assert spec.nw == base.nw and spec.native_spec()['force_regularity'] == 0
+    return spec
+
+
+def curvature2(spec, W, samples):
+    ''' k_y^2 + k_n^2 at every sample's own s, (N, S1, B), by the oracle's frame '''
+    v, _ = audit_oracle.interpolate(spec, W, samples)
+    f = audit_oracle.frame(spec, v[..., 0])
+    return np.moveaxis((f['ky'] ** 2 + f['kn'] ** 2).reshape(v.shape[:3]), 0, 2)
+
+
+@functools.lru_cache(maxsize=None)
+def case_bounds(track, model, frame, K, per_instance, B=3):
+    '''
+    Bounds of a case per component of the node vector: the problem's own (path_bounds of spec.lbw / ubw: infinite
+    on positions and velocities of the global frame), shared (NV,) or per instance (B, NV), instance b's finite
+    bounds widened by 0.1 b so the instances differ.
+    '''
+    spec = case_spec(track, model, frame, K)
+    lb, ub = path_bounds(spec)
+    if per_instance:
+        grow = 0.1 * np.arange(B)[:, None]
+        lb, ub = lb[None] - grow, ub[None] + grow
+    lb.setflags(write=False)
+    ub.setflags(write=False)
+    return lb, ub
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_val(track, model, frame, K, iset, samples, per_instance):
+    ''' the oracle's channels (NCH, N, S1, B) of one case, input set and sample count; computed once '''
+    spec = case_spec(track, model, frame, K)
+    lb, ub = case_bounds(track, model, frame, K, per_instance)
+    v = audit_oracle.audit(spec, case_inputs(track, model, frame, K)[iset], samples, lb, ub)
+    v.setflags(write=False)
+    return v
+
+
+@functools.lru_cache(maxsize=None)
+def wave_inputs(case, B):
+    ''' (W (B, nw), per-instance lb, ub) of a wave-crossing case: B no multiple of the wave or the block '''
+    W = replay_inputs(case_spec(*case), B, 4)
+    W.setflags(write=False)
+    return (W,) + case_bounds(*case, True, B)
+
+
+def rel_dev(a, ref):
+    ''' largest deviation relative to max(1, |reference value|); entries where both are the same infinity or
+    both NaN agree, where only one is they deviate infinitely '''
+    a, ref = np.asarray(a, float), np.asarray(ref, float)
+    same = (a == ref) | (np.isnan(a) & np.isnan(ref))
+    odd = ~same & ~(np.isfinite(a) & np.isfinite(ref))
+    if np.any(odd):
+        return float('inf')
+    with np.errstate(invalid='ignore'):
+        d = np.where(same, 0.0, np.abs(a - ref) / np.maximum(1.0, np.abs(ref)))
+    return float(np.max(d, initial=0.0))
+
+
+# ------------------------------------------------------------------ the hand-built between-node cases
+def _between_spec(model):
+    return case_spec('race', model, 'parametric', 2)
+
+
+def _blank(spec):
+    ''' one decision vector: the cold-start guess (every node's y, n, inputs and input rates zero) with h = 0.2 and
+    every s drawn 1 % towards the middle of [s_min, s_max], so no sample's s sits on its bound '''
+    W = np.array(spec.w0, float)[None].copy()
+    W[:, :spec.N] = 0.2
+    mid = 0.5 * (spec.line.s_min() + spec.line.s_max())
+    V = _nodes(spec, W)
+    V[..., 0] = mid + 0.99 * (V[..., 0] - mid)
+    return W
+
+
+def _nodes(spec, W):
+    V = W[:, spec.N:spec.N + spec.P * spec.nv].reshape(W.shape[0], spec.N, spec.K1, spec.nv)
+    assert np.shares_memory(V, W)
+    return V
+
+
+BETWEEN = ('corridor', 'sdot', 'thrust', 'control')
+
+
+@functools.lru_cache(maxsize=None)
+def between_case(name):
+    '''
+    (spec, W (1, nw), lb, ub) of a between-node case on the race track at K = 2, N = 3 (tau = 0 and the two
+    Gauss-Legendre points t1 = 0.2113, t2 = 0.7887, t1 + t2 = 1, t1 t2 = 1 / 6). The parabola through (c, c + a,
+    c + a) at the three nodes is c + 6 a x (1 - x): it peaks at c + 1.5 a at x = 1 / 2.
+      'corridor'  y of interval 1 = (0, y_max, y_max): on the bound at two nodes, 1.5 y_max between them
+      'thrust'    input 0 of a drone = (0.1, 1, 1) T_max: on the bound at two nodes, 1.45 T_max between them
+      'sdot'      s of interval 1 = s0 + 1.8 x - x^2 at the nodes: s' / h = (1.8 - 2 x) / h is positive at every
+                  node (0.22 / h at t2) and negative on (0.9, 1], the extrapolated tail
+      'control'   the corridor (towards y_min) and thrust vectors with a scaled by 0.6: the peaks stay at 0.9 y_min,
+                  0.91 T_max
+    '''
+    model = 'esp' if name in ('thrust', 'control') else 'point'
+    spec = _between_spec(model)
+    W = _blank(spec)
+    V = _nodes(spec, W)
+    lb, ub = path_bounds(spec)
+    tau = np.asarray(spec.tau, float)
+    scale = 0.6 if name == 'control' else 1.0
+    if name in ('corridor', 'control'):
+        # the control's y is mirrored towards y_min: on this interval the bend leaves the regularity row (channel 7)
+        # room on that side only (0.6 y_max between the nodes gives k_n y - k_y n > gamma)
+        V[0, 1, :, 1] = np.array([0.0, 1.0, 1.0]) * (ub[1] if name == 'corridor' else lb[1]) * scale
+    if name in ('thrust', 'control'):
+        c = lb[spec.nz] + 0.1 * (ub[spec.nz] - lb[spec.nz])
+        V[..., spec.nz:spec.nz + spec.nu] = c          # the cold start's zero thrust is below T_min
+        V[0, 1, :, spec.nz] = c + np.array([0.0, 1.0, 1.0]) * (ub[spec.nz] - c) * scale
+    if name == 'sdot':
+        V[0, 1, :, 0] = V[0, 1, 0, 0] + 1.8 * tau - tau ** 2
+    W.setflags(write=False)
+    return spec, W, lb, ub
+
+
+# ------------------------------------------------------------------ non-finite inputs
+@functools.lru_cache(maxsize=None)
+def nonfinite_inputs():
+    '''
+    (spec, W (6, nw)) of the parametric ESP drone on the race track, K = 2: column 0 is finite; 1: NaN in an s;
+    2: +inf in an s; 3: -inf in an s; 4: h = 0; 5: s = 1e8 and NaN in an input. Columns 1-5 must not pass.
+    '''
+    spec = case_spec('race', 'esp', 'parametric', 2)
+    W = np.repeat(case_inputs('race', 'esp', 'parametric', 2)[0][:1], 6, axis=0).copy()
+    V = _nodes(spec, W)
+    V[1, 1, 1, 0] = np.nan
+    V[2, 1, 1, 0] = np.inf
+    V[3, 1, 1, 0] = -np.inf
+    W[4, 1] = 0.0
+    V[5, 0, 1, 0] = 1e8
+    V[5, 2, 0, spec.nz + 1] = np.nan
+    W.setflags(write=False)
+    return spec, W

@@ -4,7 +4,8 @@ Build libato.so for gfx950 in-tree (aircraft_trajectory_optimization_amd/_lib/).
 One object per model variant (ato_inst.hip, -DATO_INST=i) plus the C-ABI object, compiled
 in parallel with hipcc, the replay kernels (ato_replay.hip), the mesh-transfer kernel (ato_remesh.hip), the clearance kernel (ato_clearance.hip), the audit kernel (ato_audit.hip), and the host-only Hessian structure analysis (ato_hstruct.cpp, g++),
 then linked into a shared library. Objects are rebuilt only when
-a source or header is newer.
+a source or header is newer (every csrc/*.hpp counts, ato_sample.hpp, the layer the four post-solve kernels share,
+included).
 '''
 import glob
 import os

@@ -4,7 +4,7 @@
 // collocation polynomial is interpolated at abscissa x_i,
 //   v = sum_j l_j(x_i) V[n, j, .],        zp = sum_j l_j'(x_i) Z[n, j, .] / h_n,
 // x_i = i / S for samples = S >= 1 (S + 1 points, both ends) or the nodes tau_0 .. tau_K for samples = 0 (the
-// sample abscissae of the clearance, ato_clearance.hpp). At the nodes l_j(tau_k) is exactly delta_jk and the
+// clearance's abscissae: clearance_points, ato_sample.hpp). At the nodes l_j(tau_k) is exactly delta_jk and the
 // derivative weights are the problem's own C table (dw[k][j] = C[j][k]), so the node audit evaluates the NLP's
 // own polynomial derivative. In parametric problems the node geometry (R_p, k_s, k_y, k_n, |x_c'|) is
 // frame_from_terms of the centreline's two piecewise cubics (ato_clearance_set_line) AT THE SAMPLE'S OWN
@@ -40,11 +40,11 @@
 //
 // Shared by the HIP kernel (k_audit, ato_audit.hip) and the CPU twin (tests/native/audit_hostcheck.cpp):
 // audit_point() is ATO_HD. Interpolation sums, Horner steps, dot and cross products are explicit fused
-// multiply-adds in a fixed order. Every table read is indexed by n, i, j or by clearance_piece()'s result,
+// multiply-adds in a fixed order. Every table read is indexed by n, i, j or by line_piece()'s result,
 // which lies in [0, n_knots] for any s (NaN and +-inf included): no input value can move a read outside its
 // table. Nothing renormalises or clips; outputs may be NaN or inf.
 #pragma once
-#include "ato_clearance.hpp"
+#include "ato_sample.hpp"
 
 namespace ato {
 
@@ -56,34 +56,20 @@ struct AuditD {
     int32_t N, K1, NV, S1, nw, force_reg, bounds_per_instance;
     double gamma;
     Vehicle veh;
-    const double* wt;      // [S1][K1] l_j(x_i)
-    const double* dw;      // [S1][K1] l_j'(x_i)
+    const double* wt;      // [S1][K1] l_j(x_i)   (clearance_weights)
+    const double* dw;      // [S1][K1] l_j'(x_i)  (audit_dweights)
     const double *lb, *ub; // NULL: no bounds
     LineD line;
 };
 
-// l_j'(x_i) = sum_{m != j} 1 / (tau_j - tau_m) prod_{r != j, m} (x - tau_r) / (tau_j - tau_r), m and r
-// ascending; with samples = 0 the problem's own table, dw[k][j] = C[j][k]. Host side, fp64.
+// [S1][K1] l_j'(x_i) (lagrange_drow); with samples = 0 the problem's own table, dw[k][j] = C[j][k]. Host side, fp64.
 inline void audit_dweights(const double* tau, const double* C, int K1, int samples, double* dw) {
     const int S1 = clearance_points(K1, samples);
     for (int i = 0; i < S1; ++i) {
-        const double x = samples == 0 ? tau[i] : (double)i / (double)samples;
-        for (int j = 0; j < K1; ++j) {
-            if (samples == 0) {
-                dw[i * K1 + j] = C[j * K1 + i];
-                continue;
-            }
-            double acc = 0.0;
-            for (int m = 0; m < K1; ++m) {
-                if (m == j) continue;
-                double v = 1.0 / (tau[j] - tau[m]);
-                for (int r = 0; r < K1; ++r) {
-                    if (r == j || r == m) continue;
-                    v *= (x - tau[r]) / (tau[j] - tau[r]);
-                }
-                acc += v;
-            }
-            dw[i * K1 + j] = acc;
+        if (samples == 0) {
+            for (int j = 0; j < K1; ++j) dw[i * K1 + j] = C[j * K1 + i];
+        } else {
+            lagrange_drow(tau, K1, sample_abscissa(tau, samples, i), dw + (long)i * K1);
         }
     }
 }
@@ -92,22 +78,12 @@ inline void audit_dweights(const double* tau, const double* C, int K1, int sampl
 inline int audit_check(const ProbD& p, bool has_line, int batch, int layout, int samples, bool has_lb, bool has_ub,
                        const char** msg) {
     *msg = "";
-    if (batch < 1) { *msg = "batch must be >= 1"; return ATO_ERR_ARG; }
-    if (layout != ATO_LAYOUT_INTERLEAVED && layout != ATO_LAYOUT_INSTANCE_MAJOR) {
-        *msg = "unknown layout";
-        return ATO_ERR_ARG;
-    }
-    if (samples < 0 || samples > CLEAR_SMAX) { *msg = "samples must be in [0, 64]"; return ATO_ERR_ARG; }
+    if (int rc = check_batch(batch, msg)) return rc;
+    if (int rc = check_layout(layout, msg)) return rc;
+    if (int rc = check_samples(samples, msg)) return rc;
     if (has_lb != has_ub) { *msg = "lb and ub must both be given or both be NULL"; return ATO_ERR_ARG; }
-    if (p.trans != ATO_TRANS_COLLOCATION) {
-        *msg = "audit of RK4-transcribed problems (K = 0) is not supported";
-        return ATO_ERR_UNSUPPORTED;
-    }
-    if (p.frame != GLOBAL && !has_line) {
-        *msg = "parametric audit needs the centreline table (ato_clearance_set_line)";
-        return ATO_ERR_STATE;
-    }
-    return ATO_OK;
+    if (int rc = check_collocation(p, "audit of RK4-transcribed problems (K = 0) is not supported", msg)) return rc;
+    return check_line(p, has_line, "parametric audit needs the centreline table (ato_clearance_set_line)", msg);
 }
 
 inline AuditD audit_args(const ProbD& p, int samples, const double* wt, const double* dw, const LineD& line,
@@ -116,60 +92,29 @@ inline AuditD audit_args(const ProbD& p, int samples, const double* wt, const do
                   p.gamma, p.veh, wt, dw, lb, ub, line};
 }
 
-// value, first and second derivative (d, dd may be NULL) of a piecewise cubic at s; the sibling of
-// clearance_cubic (same piece, same Horner steps for v and d). The extrapolation pieces carry no quadratic or
-// cubic coefficient, so their second derivative is zero.
-ATO_HD void audit_cubic(const double* __restrict__ k, const double* __restrict__ c, int nk, double s, double* v,
-                        double* d, double* dd) {
-    const int pc = clearance_piece(k, nk, s);
-    const double x = s - k[pc > 0 ? pc - 1 : 0];
-    const double* q = c + (long)pc * 12;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double c0 = q[a], c1 = q[3 + a], c2 = q[6 + a], c3 = q[9 + a];
-        v[a] = fma(fma(fma(c3, x, c2), x, c1), x, c0);
-        if (d) d[a] = fma(fma(3.0 * c3, x, 2.0 * c2), x, c1);
-        if (dd) dd[a] = fma(6.0 * c3, x, 2.0 * c2);
-    }
-}
-
-ATO_HD void audit_cross(const double* a, const double* b, double* o) {
-    o[0] = fma(a[1], b[2], -(a[2] * b[1]));
-    o[1] = fma(a[2], b[0], -(a[0] * b[2]));
-    o[2] = fma(a[0], b[1], -(a[1] * b[0]));
-}
-
-// frame_from_terms (centerlines/base_centerline.py) at s: Rp = [e_s e_y e_n] row-major, k_s, k_y, k_n, |x_c'|
+// frame_from_terms (centerlines/base_centerline.py) at s: Rp = [e_s e_y e_n] row-major, k_s, k_y, k_n, |x_c'|:
+// the frame of the sampling layer and the curvatures from x_c'' and r_y'
 ATO_HD void audit_geom(const LineD& L, double s, NodeGeom<double>& G) {
-    double xc[3], xs[3], xss[3], ry[3], rys[3], es[3], ey[3], en[3], cr[3];
-    audit_cubic(L.kx, L.cx, L.nx, s, xc, xs, xss);
-    audit_cubic(L.kr, L.cr, L.nr, s, ry, rys, nullptr);
-    const double mag = sqrt(clearance_dot(xs, xs));
-#pragma unroll
-    for (int a = 0; a < 3; ++a) es[a] = xs[a] / mag;
-    const double pr = clearance_dot(es, ry);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) ey[a] = fma(-es[a], pr, ry[a]);
-    const double my = sqrt(clearance_dot(ey, ey));
-#pragma unroll
-    for (int a = 0; a < 3; ++a) ey[a] = ey[a] / my;
-    audit_cross(es, ey, en);
-    const double a_ = clearance_dot(xs, es), b_ = clearance_dot(xs, ey);
-    const double c_ = clearance_dot(ry, es), d_ = clearance_dot(ry, ey);
-    const double r0 = clearance_dot(xss, en), r1 = clearance_dot(rys, en);
+    LineFrame F;
+    double xss[3], rys[3], cr[3];
+    line_frame(L, s, F, xss, rys);
+    const double mag = F.mag;
+    const double a_ = dot3(F.xs, F.es), b_ = dot3(F.xs, F.ey);
+    const double c_ = dot3(F.ry, F.es), d_ = dot3(F.ry, F.ey);
+    const double r0 = dot3(xss, F.en), r1 = dot3(rys, F.en);
     const double det = fma(a_, d_, -(b_ * c_));
     const double kyks0 = fma(d_, r0, -(b_ * r1)) / det / mag;
     const double kyks1 = fma(a_, r1, -(c_ * r0)) / det / mag;
-    audit_cross(xss, xs, cr);
-    G.kn = -clearance_dot(cr, en) / (mag * mag * mag);
+    cross3(xss, F.xs, cr);
+    G.kn = -dot3(cr, F.en) / (mag * mag * mag);
     G.ks = kyks1;
     G.ky = -kyks0;
     G.mag = mag;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        G.Rp[a * 3 + 0] = es[a];
-        G.Rp[a * 3 + 1] = ey[a];
-        G.Rp[a * 3 + 2] = en[a];
+        G.Rp[a * 3 + 0] = F.es[a];
+        G.Rp[a * 3 + 1] = F.ey[a];
+        G.Rp[a * 3 + 2] = F.en[a];
     }
 }
 
@@ -240,10 +185,7 @@ ATO_HD void audit_point(const AuditD& a, int n, int i, int b, int B, bool il, co
         const bool reg = fma(G.ky, G.ky, G.kn * G.kn) > 0.1 || a.force_reg;
         out[7] = reg ? a.gamma - fma(G.kn, v[1], -(G.ky * v[2])) : inf;
     } else {
-#pragma unroll
-        for (int c = 0; c < 9; ++c) G.Rp[c] = 0.0;
-        G.ks = G.ky = G.kn = 0.0;
-        G.mag = 1.0;
+        G = flat_geom();
         out[6] = inf;
         out[7] = inf;
     }

@@ -55,12 +55,10 @@ static void release(ato_handle* h) {
     (void)hipFree(h->d_dJ);
     (void)hipFree(h->d_dgf);
     (void)hipFree(h->d_lift);
-    (void)hipFree(h->d_replay_w);
     for (auto& kv : h->remesh_tabs) (void)hipFree(kv.second.dev);
     (void)hipFree(h->d_line);
-    (void)hipFree(h->d_clear_w);
     (void)hipFree(h->d_clear_pos);
-    (void)hipFree(h->d_audit_w);
+    for (ato_weight_cache* c : {&h->replay_w, &h->clear_w, &h->audit_w}) (void)hipFree(c->dev);
     h->remesh_tabs.clear();
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
     h->events.clear();
@@ -133,27 +131,22 @@ static int create_impl(const ato_problem_desc* desc, ato_handle** out) {
         delete h;
         return rc;
     }
-    // the replay's weight table, sized for the largest substep count: ato_replay itself allocates nothing
-    if (hipMalloc((void**)&h->d_replay_w, (size_t)(2 * ato::REPLAY_SMAX + 1) * (ATO_KMAX + 1) * sizeof(double)) !=
-        hipSuccess) {
-        release(h);
-        delete h;
-        return fail(ATO_ERR_HIP, "replay weight table: out of device memory");
-    }
-    // the clearance's weight table likewise
-    if (hipMalloc((void**)&h->d_clear_w, (size_t)(ato::CLEAR_SMAX + 1) * (ATO_KMAX + 1) * sizeof(double)) !=
-        hipSuccess) {
-        release(h);
-        delete h;
-        return fail(ATO_ERR_HIP, "clearance weight table: out of device memory");
-    }
-    // the audit's two weight tables likewise
-    if (hipMalloc((void**)&h->d_audit_w, (size_t)2 * (ato::CLEAR_SMAX + 1) * (ATO_KMAX + 1) * sizeof(double)) !=
-        hipSuccess) {
-        release(h);
-        delete h;
-        return fail(ATO_ERR_HIP, "audit weight tables: out of device memory");
-    }
+    // the weight tables of the replay, the clearance and the audit (value and derivative), sized for the largest
+    // substep / sample count: the calls themselves allocate nothing
+    const size_t row = (ATO_KMAX + 1) * sizeof(double);
+    const struct {
+        ato_weight_cache* cache;
+        size_t rows;
+        const char* what;
+    } caches[] = {{&h->replay_w, 2 * ato::SAMPLE_SMAX + 1, "replay weight table: out of device memory"},
+                  {&h->clear_w, ato::SAMPLE_SMAX + 1, "clearance weight table: out of device memory"},
+                  {&h->audit_w, 2 * (ato::SAMPLE_SMAX + 1), "audit weight tables: out of device memory"}};
+    for (const auto& c : caches)
+        if (hipMalloc((void**)&c.cache->dev, c.rows * row) != hipSuccess) {
+            release(h);
+            delete h;
+            return fail(ATO_ERR_HIP, c.what);
+        }
     h->pd = h->L.p;
     h->pd.geom = h->d_geom;
     h->pd.node_s = h->d_node_s;
@@ -457,16 +450,9 @@ static int replay_impl(ato_handle* h, int32_t batch, int32_t layout, const doubl
     if (int rc = ato::replay_check(p, h->d_lift != nullptr, batch, layout, substeps, &msg)) return fail(rc, msg);
     if (!w || !zsim || !err) return fail(ATO_ERR_ARG, "null buffer");
     hipStream_t st = (hipStream_t)stream;
-    if (h->replay_S != substeps) {
-        std::vector<double>& tab = h->replay_w_host[substeps];
-        if (tab.empty()) {
-            tab.resize((size_t)(2 * substeps + 1) * p.K1);
-            ato::replay_weights(p.tau, p.K1, substeps, tab.data());
-        }
-        ATO_HIP(hipMemcpyAsync(h->d_replay_w, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        h->replay_S = substeps;
-    }
-    const ato::ReplayD r{substeps, traj ? 1 : 0, h->d_replay_w, p.frame == ato::GLOBAL ? nullptr : h->d_lift};
+    ATO_HIP(h->replay_w.use(substeps, (size_t)(2 * substeps + 1) * p.K1,
+                            [&](double* lw) { ato::replay_weights(p.tau, p.K1, substeps, lw); }, st));
+    const ato::ReplayD r{substeps, traj ? 1 : 0, h->replay_w.dev, p.frame == ato::GLOBAL ? nullptr : h->d_lift};
     hipError_t e = hipSuccess;
     ato::with_model(p, [&]<class M>() { e = ato::launch_replay<M>(p, r, batch, layout, w, zsim, err, traj, st); });
     if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("replay launch: ") + hipGetErrorString(e));
@@ -520,12 +506,7 @@ static int clearance_set_line_impl(ato_handle* h, const ato_line_table* t) {
     if (h->L.p.frame == ato::GLOBAL) return ATO_OK;      // not needed: ignored
     if (t->n_xc < 2 || t->n_ry < 2 || !t->xc_knots || !t->xc_coef || !t->ry_knots || !t->ry_coef)
         return fail(ATO_ERR_ARG, "bad centreline table");
-    const size_t nx = (size_t)t->n_xc, nr = (size_t)t->n_ry;
-    std::vector<double> buf;
-    buf.insert(buf.end(), t->xc_knots, t->xc_knots + nx);
-    buf.insert(buf.end(), t->xc_coef, t->xc_coef + (nx + 1) * 12);
-    buf.insert(buf.end(), t->ry_knots, t->ry_knots + nr);
-    buf.insert(buf.end(), t->ry_coef, t->ry_coef + (nr + 1) * 12);
+    const std::vector<double> buf = ato::line_pack(*t);
     double* d = nullptr;
     ATO_HIP(hipMalloc((void**)&d, buf.size() * sizeof(double)));
     if (hipMemcpy(d, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
@@ -538,7 +519,7 @@ static int clearance_set_line_impl(ato_handle* h, const ato_line_table* t) {
     }
     (void)hipFree(h->d_line);
     h->d_line = d;
-    h->line = ato::LineD{t->n_xc, t->n_ry, d, d + nx, d + nx + (nx + 1) * 12, d + nx + (nx + 1) * 12 + nr};
+    h->line = ato::line_view(*t, d);
     return ATO_OK;
 }
 
@@ -569,16 +550,9 @@ static int clearance_impl(ato_handle* h, ato_mesh* mesh, int32_t batch, int32_t 
         }
         pos = h->d_clear_pos;
     }
-    if (h->clear_samples != samples) {
-        std::vector<double>& tab = h->clear_w_host[samples];
-        if (tab.empty()) {
-            tab.resize((size_t)S1 * p.K1);
-            ato::clearance_weights(p.tau, p.K1, samples, tab.data());
-        }
-        ATO_HIP(hipMemcpyAsync(h->d_clear_w, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        h->clear_samples = samples;
-    }
-    const ato::ClearD a = ato::clearance_args(p, samples, h->d_clear_w, h->line);
+    ATO_HIP(h->clear_w.use(samples, (size_t)S1 * p.K1,
+                           [&](double* wt) { ato::clearance_weights(p.tau, p.K1, samples, wt); }, st));
+    const ato::ClearD a = ato::clearance_args(p, samples, h->clear_w.dev, h->line);
     const hipError_t e = ato::launch_clearance_pos(a, batch, layout, w, pos, st);
     if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("clearance launch: ") + hipGetErrorString(e));
     if (!dist) return ATO_OK;
@@ -601,20 +575,13 @@ static int audit_impl(ato_handle* h, int32_t batch, int32_t layout, const double
         return fail(rc, msg);
     if (!w || !val) return fail(ATO_ERR_ARG, "null buffer");
     hipStream_t st = (hipStream_t)stream;
-    const int S1 = ato::clearance_points(p.K1, samples);
-    const size_t len = (size_t)S1 * p.K1;
-    if (h->audit_samples != samples) {
-        std::vector<double>& tab = h->audit_w_host[samples];
-        if (tab.empty()) {
-            tab.resize(2 * len);
-            ato::clearance_weights(p.tau, p.K1, samples, tab.data());
-            ato::audit_dweights(p.tau, p.C, p.K1, samples, tab.data() + len);
-        }
-        ATO_HIP(hipMemcpyAsync(h->d_audit_w, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        h->audit_samples = samples;
-    }
+    const size_t len = (size_t)ato::clearance_points(p.K1, samples) * p.K1;
+    ATO_HIP(h->audit_w.use(samples, 2 * len, [&](double* tab) {
+        ato::clearance_weights(p.tau, p.K1, samples, tab);
+        ato::audit_dweights(p.tau, p.C, p.K1, samples, tab + len);
+    }, st));
     const ato::AuditD a =
-        ato::audit_args(p, samples, h->d_audit_w, h->d_audit_w + len, h->line, lb, ub, bounds_per_instance);
+        ato::audit_args(p, samples, h->audit_w.dev, h->audit_w.dev + len, h->line, lb, ub, bounds_per_instance);
     hipError_t e = hipErrorInvalidValue;
     ato::with_model(p, [&]<class M>() { e = ato::launch_audit<M>(a, batch, layout, w, val, st); });
     if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("audit launch: ") + hipGetErrorString(e));

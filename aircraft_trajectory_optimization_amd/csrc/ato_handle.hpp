@@ -9,6 +9,29 @@
 #include "ato_clearance.hpp"
 #include "ato_audit.hpp"
 
+// A Lagrange weight table on the device, keyed by a substep or sample count. dev is allocated once (ato_create,
+// sized for the largest key) and holds the table of the key last uploaded; the host tables it is uploaded from
+// are made on first use and never rewritten or dropped (an upload may still be queued on a stream).
+struct ato_weight_cache {
+    double* dev = nullptr;
+    int32_t key = -1;
+    std::map<int32_t, std::vector<double>> host;
+    // make dev hold the table of `key`: len doubles, written by fill(double*) the first time the key is seen,
+    // uploaded on st only when the key changes; a warm call does nothing
+    template <class Fill>
+    hipError_t use(int32_t k, size_t len, Fill&& fill, hipStream_t st) {
+        if (key == k) return hipSuccess;
+        std::vector<double>& tab = host[k];
+        if (tab.empty()) {
+            tab.resize(len);
+            fill(tab.data());
+        }
+        const hipError_t e = hipMemcpyAsync(dev, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) key = k;
+        return e;
+    }
+};
+
 struct ato_handle {
     ato::Layout L;
     int device = 0;
@@ -51,13 +74,10 @@ struct ato_handle {
     double* d_dgf = nullptr;
     int32_t hess_reserved = 0;
     int32_t hess_colors = 0;
-    // replay (ato_replay.hpp): lift table [N+1][12] (parametric problems), the Lagrange weight table of
-    // the substep count last used (sized for REPLAY_SMAX) and the host tables it is uploaded from, one
-    // per substep count and never rewritten (an upload may still be queued on a stream)
+    // replay (ato_replay.hpp): lift table [N+1][12] (parametric problems) and the weight table [2 S + 1][K + 1]
+    // by substep count S
     double* d_lift = nullptr;
-    double* d_replay_w = nullptr;
-    int32_t replay_S = 0;
-    std::map<int32_t, std::vector<double>> replay_w_host;
+    ato_weight_cache replay_w;
     // mesh transfer INTO this problem (ato_remesh.hpp): one weight table [r][K' + 1][K + 1] per source
     // discretisation, keyed by (r, the source's tau_0 .. tau_K); allocated and uploaded by the first call
     // with that key, on that call's stream, and never rewritten or freed before the handle
@@ -67,19 +87,13 @@ struct ato_handle {
     };
     std::map<std::vector<double>, RemeshTable> remesh_tabs;
     // clearance (ato_clearance.hpp): the centreline's two piecewise cubics (ato_clearance_set_line, one
-    // allocation: knots and coefficients back to back), the weight table of the sample count last used (sized
-    // for CLEAR_SMAX, uploaded from per-count host tables that are never rewritten) and the position buffer of
-    // calls that pass pos = NULL (grown only when a call needs more)
+    // allocation: line_pack), the weight table [S1][K + 1] by sample count and the position buffer of calls that
+    // pass pos = NULL (grown only when a call needs more)
     double* d_line = nullptr;
     ato::LineD line{};
-    double* d_clear_w = nullptr;
-    int32_t clear_samples = -1;
-    std::map<int32_t, std::vector<double>> clear_w_host;
+    ato_weight_cache clear_w;
     double* d_clear_pos = nullptr;
     size_t clear_pos_len = 0;
-    // audit (ato_audit.hpp): value and derivative weight tables of the sample count last used, back to back
-    // in one allocation sized for CLEAR_SMAX, uploaded from per-count host tables that are never rewritten
-    double* d_audit_w = nullptr;
-    int32_t audit_samples = -1;
-    std::map<int32_t, std::vector<double>> audit_w_host;
+    // audit (ato_audit.hpp): value and derivative weight tables by sample count, back to back
+    ato_weight_cache audit_w;
 };

@@ -5,7 +5,7 @@
 //   h'[n r + j]     = h[n] / r
 //   v'[n r + j, k'] = sum_m l_m((j + tau'_k') / r) v[n, m]        for every per-node variable v
 // (the NZ states, the NU inputs and the NU input rates: everything Cols<M> addresses per node), with
-// l_m the Lagrange basis over the source nodes tau_0 = 0, tau_1 .. tau_K: the interpolant of
+// l_m the Lagrange basis over the source nodes tau_0 = 0, tau_1 .. tau_K (ato_sample.hpp): the interpolant of
 // interpolate_collocation and of the replay's input. Nothing is renormalised or clipped.
 //
 // One work item = (instance, source interval n, per-node variable v), v == NV being the interval's h:
@@ -16,8 +16,7 @@
 // contract; l_m(tau_k) is exactly delta_mk, so the identity transfer (r = 1, K' = K) is bitwise for
 // finite inputs.
 #pragma once
-#include <cmath>
-#include "ato_program.hpp"
+#include "ato_sample.hpp"
 
 namespace ato {
 
@@ -28,44 +27,31 @@ struct RemeshD {
     const double* wt;               // [r][K1d][K1s] weights l_m((j + tau'_k') / r)
 };
 
-// l_m((j + tau'_k') / r) as the product over r' != m (ascending) of (x - tau_r') / (tau_m - tau_r'): the
-// formula of replay_weights; host side, fp64: the one table the kernel, the twin and the test oracle use
+// l_m((j + tau'_k') / r) over the source nodes (lagrange_row): the one table the kernel, the twin and the test
+// oracle use
 inline void remesh_weights(const double* tau_s, int K1s, const double* tau_d, int K1d, int r, double* wt) {
     for (int j = 0; j < r; ++j)
-        for (int k = 0; k < K1d; ++k) {
-            const double x = ((double)j + tau_d[k]) / (double)r;
-            for (int m = 0; m < K1s; ++m) {
-                double v = 1.0;
-                for (int q = 0; q < K1s; ++q) {
-                    if (q == m) continue;
-                    v *= (x - tau_s[q]) / (tau_s[m] - tau_s[q]);
-                }
-                wt[((long)j * K1d + k) * K1s + m] = v;
-            }
-        }
+        for (int k = 0; k < K1d; ++k)
+            lagrange_row(tau_s, K1s, ((double)j + tau_d[k]) / (double)r, wt + ((long)j * K1d + k) * K1s);
 }
 
 // 0 (ATO_OK) or the error code of an ato_remesh call with these arguments; *msg gets the reason
 inline int remesh_check(const ProbD& s, const ProbD& d, int batch_src, int batch_dst, bool has_cols, int layout,
                         const char** msg) {
+    const char* const rk4 = "transfer of RK4-transcribed problems (K = 0) is not supported";
     *msg = "";
-    if (batch_src < 1 || batch_dst < 1) { *msg = "batch must be >= 1"; return ATO_ERR_ARG; }
+    if (int rc = check_batch(batch_src < batch_dst ? batch_src : batch_dst, msg)) return rc;
     if (!has_cols && batch_src != batch_dst) {
         *msg = "without a column map the two batches must be equal";
         return ATO_ERR_ARG;
     }
-    if (layout != ATO_LAYOUT_INTERLEAVED && layout != ATO_LAYOUT_INSTANCE_MAJOR) {
-        *msg = "unknown layout";
-        return ATO_ERR_ARG;
-    }
+    if (int rc = check_layout(layout, msg)) return rc;
     if (s.model != d.model || s.att != d.att || s.frame != d.frame || s.NV != d.NV) {
         *msg = "source and destination must have the same model variant (model, attitude, frame)";
         return ATO_ERR_ARG;
     }
-    if (s.trans != ATO_TRANS_COLLOCATION || d.trans != ATO_TRANS_COLLOCATION) {
-        *msg = "transfer of RK4-transcribed problems (K = 0) is not supported";
-        return ATO_ERR_UNSUPPORTED;
-    }
+    if (int rc = check_collocation(s, rk4, msg)) return rc;
+    if (int rc = check_collocation(d, rk4, msg)) return rc;
     if (s.cpc_m > 0 || d.cpc_m > 0) {
         *msg = "transfer of CPC progress variables is not supported";
         return ATO_ERR_UNSUPPORTED;

@@ -19,11 +19,10 @@
 // replay_interval() is ATO_HD. Nothing renormalises the quaternion or the DCM on the way: the drift
 // is part of what is reported.
 #pragma once
-#include "ato_program.hpp"
+#include "ato_sample.hpp"
 
 namespace ato {
 
-constexpr int REPLAY_SMAX = 64;       // substeps per interval
 constexpr int REPLAY_LIFT_W = 12;     // doubles per boundary in the lift table
 
 // replay arguments next to ProbD (kernel argument)
@@ -34,35 +33,18 @@ struct ReplayD {
     const double* lift;    // [N + 1][REPLAY_LIFT_W]; NULL: global-frame problem
 };
 
-// l_j(i / (2 S)), i = 0 .. 2 S, as the product over r != j (ascending) of (x - tau_r) / (tau_j - tau_r);
-// host side, fp64: the one table the kernel, the twin and the test oracle all use
+// l_j(i / (2 S)), i = 0 .. 2 S (lagrange_row): the one table the kernel, the twin and the test oracle all use
 inline void replay_weights(const double* tau, int K1, int S, double* lw) {
-    for (int i = 0; i <= 2 * S; ++i) {
-        const double x = (double)i / (double)(2 * S);
-        for (int j = 0; j < K1; ++j) {
-            double v = 1.0;
-            for (int r = 0; r < K1; ++r) {
-                if (r == j) continue;
-                v *= (x - tau[r]) / (tau[j] - tau[r]);
-            }
-            lw[i * K1 + j] = v;
-        }
-    }
+    for (int i = 0; i <= 2 * S; ++i) lagrange_row(tau, K1, (double)i / (double)(2 * S), lw + (long)i * K1);
 }
 
 // 0 (ATO_OK) or the error code of an ato_replay call with these arguments; *msg gets the reason
 inline int replay_check(const ProbD& p, bool has_lift, int batch, int layout, int substeps, const char** msg) {
     *msg = "";
-    if (batch < 1) { *msg = "batch must be >= 1"; return ATO_ERR_ARG; }
-    if (layout != ATO_LAYOUT_INTERLEAVED && layout != ATO_LAYOUT_INSTANCE_MAJOR) {
-        *msg = "unknown layout";
-        return ATO_ERR_ARG;
-    }
-    if (substeps < 1 || substeps > REPLAY_SMAX) { *msg = "substeps must be in [1, 64]"; return ATO_ERR_ARG; }
-    if (p.trans != ATO_TRANS_COLLOCATION) {
-        *msg = "replay of RK4-transcribed problems (K = 0) is not supported";
-        return ATO_ERR_UNSUPPORTED;
-    }
+    if (int rc = check_batch(batch, msg)) return rc;
+    if (int rc = check_layout(layout, msg)) return rc;
+    if (substeps < 1 || substeps > SAMPLE_SMAX) { *msg = "substeps must be in [1, 64]"; return ATO_ERR_ARG; }
+    if (int rc = check_collocation(p, "replay of RK4-transcribed problems (K = 0) is not supported", msg)) return rc;
     if (p.frame == PARAM_REL) {
         *msg = "replay of parametric problems with the relative attitude (global_r = 0) is not supported";
         return ATO_ERR_UNSUPPORTED;
@@ -146,11 +128,7 @@ ATO_HD void replay_interval(const ProbD& p, const ReplayD& r, int n, const W& w,
         }
     };
 
-    NodeGeom<double> geo;       // the global models read no geometry
-#pragma unroll
-    for (int i = 0; i < 9; ++i) geo.Rp[i] = 0.0;
-    geo.ks = geo.ky = geo.kn = 0.0;
-    geo.mag = 1.0;
+    const NodeGeom<double> geo = flat_geom();
 
     double ua[NU], um[NU], ub[NU];
     input(0, ua);

@@ -355,6 +355,12 @@ class NativeProblem:
         if rc != 0:
             raise RuntimeError(f'libato error {rc}: {self.lib.ato_last_error().decode()}')
 
+    def _check_supported(self, rc):
+        ''' as _check; a problem the call does not cover (ATO_ERR_UNSUPPORTED) raises NotImplementedError '''
+        if rc == ATO_ERR_UNSUPPORTED:
+            raise NotImplementedError(self.lib.ato_last_error().decode())
+        self._check(rc)
+
     def sparsity(self) -> Tuple[np.ndarray, np.ndarray]:
         ''' CSR (row_ptr[ng+1], col[nnz]) '''
         rp = ctypes.POINTER(ctypes.c_int32)()
@@ -449,9 +455,7 @@ class NativeProblem:
         message.
         '''
         rc = self.replay_rc(batch, w, substeps, zsim, err, traj, layout, stream)
-        if rc == ATO_ERR_UNSUPPORTED:
-            raise NotImplementedError(self.lib.ato_last_error().decode())
-        self._check(rc)
+        self._check_supported(rc)
 
     def remesh_rc(self, src: 'NativeProblem', batch_src: int, batch_dst: int, w_src: int, w_dst: int, cols: int = 0,
                   layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0) -> int:
@@ -469,9 +473,7 @@ class NativeProblem:
         NotImplementedError with the library's message.
         '''
         rc = self.remesh_rc(src, batch_src, batch_dst, w_src, w_dst, cols, layout, stream)
-        if rc == ATO_ERR_UNSUPPORTED:
-            raise NotImplementedError(self.lib.ato_last_error().decode())
-        self._check(rc)
+        self._check_supported(rc)
 
     def clearance_set_line(self, table: dict):
         ''' centreline table of a parametric problem (ProblemSpec.line_table), copied '''
@@ -494,9 +496,7 @@ class NativeProblem:
         library's message.
         '''
         rc = self.clearance_rc(batch, w, samples, pos, dist, mesh, cull, layout, stream)
-        if rc == ATO_ERR_UNSUPPORTED:
-            raise NotImplementedError(self.lib.ato_last_error().decode())
-        self._check(rc)
+        self._check_supported(rc)
 
     def audit_rc(self, batch: int, w: int, samples: int, val: int, lb: int = 0, ub: int = 0,
                  bounds_per_instance: bool = False, layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0) -> int:
@@ -514,9 +514,7 @@ class NativeProblem:
         NotImplementedError with the library's message.
         '''
         rc = self.audit_rc(batch, w, samples, val, lb, ub, bounds_per_instance, layout, stream)
-        if rc == ATO_ERR_UNSUPPORTED:
-            raise NotImplementedError(self.lib.ato_last_error().decode())
-        self._check(rc)
+        self._check_supported(rc)
 
     def timing_start(self, max_calls: int):
         ''' record HIP events around the kernels of the next max_calls evaluations '''

@@ -5,7 +5,6 @@ the GPU tests share (those of the clearance tests), their inputs, bounds and the
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 
@@ -13,7 +12,7 @@ from aircraft_trajectory_optimization_amd import native
 from aircraft_trajectory_optimization_amd.raceline.audit import path_bounds
 from tests import audit_oracle
 from tests.clearance_helpers import CASES, IL, IM, SAMPLES, case_id, case_inputs, case_spec, n_points, node_s_view  # noqa: F401
-from tests.helpers import REPO
+from tests.helpers import REPO, build_twin
 from tests.replay_helpers import replay_inputs
 
 AUDIT_SRC = os.path.join(REPO, 'tests', 'native', 'audit_hostcheck.cpp')
@@ -56,16 +55,7 @@ SEG_SDOT, SEG_ODE_A, SEG_ODE_B, SEG_REG, SEG_STAGE = 0, 1, 2, 4, 5      # ato::S
 
 
 def build_auditcheck(force=False):
-    ''' the twin, with the g++ line of helpers.build_hostcheck '''
-    csrc = os.path.join(REPO, 'aircraft_trajectory_optimization_amd', 'csrc')
-    srcs = [AUDIT_SRC] + [os.path.join(csrc, f) for f in ('ato_models.hpp', 'ato_dual.hpp', 'ato_program.hpp',
-                                                         'ato_layout.hpp', 'ato_clearance.hpp', 'ato_audit.hpp')]
-    if not force and os.path.exists(AUDIT_LIB) and \
-            os.path.getmtime(AUDIT_LIB) >= max(os.path.getmtime(s) for s in srcs):
-        return AUDIT_LIB
-    subprocess.check_call(['g++', '-std=c++20', '-O3', '-march=x86-64-v3', '-fopenmp', '-fPIC', '-shared', '-o',
-                           AUDIT_LIB, AUDIT_SRC])
-    return AUDIT_LIB
+    return build_twin(AUDIT_SRC, AUDIT_LIB, ('ato_sample.hpp', 'ato_audit.hpp'), force)
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,6 +1,6 @@
 '''
-ORACLE (test infrastructure only) of the between-node audit: numpy restatement of the sample abscissae and the
-two weight formulas, the Lagrange sums, the product's own line.param_terms with frame_from_terms for the
+ORACLE (test infrastructure only) of the between-node audit: numpy restatement of the sample abscissae, the
+Lagrange basis and its derivative (tests/lagrange_oracle.py), the Lagrange sums, the product's own line.param_terms with frame_from_terms for the
 geometry at each sample's s, oracle.ref_models for f, and the bounds by plain comparisons. Independent of
 csrc/ato_audit.hpp: only the definition in include/ato.h is shared.
 '''
@@ -8,6 +8,7 @@ import numpy as np
 
 from aircraft_trajectory_optimization_amd.centerlines.base_centerline import frame_from_terms
 from oracle import ref_models
+from tests import lagrange_oracle
 from tests.clearance_oracle import abscissae, weights
 from tests.replay_oracle import _att, _veh
 
@@ -15,24 +16,10 @@ NCH = 14
 
 
 def dweights(spec, samples):
-    ''' [S1][K1] l_j'(x_i) = sum over m != j of 1 / (tau_j - tau_m) prod over r != j, m of (x - tau_r) / (tau_j -
-    tau_r); at the nodes (samples = 0) the problem's own C table, dw[k][j] = C[j][k] '''
+    ''' [S1][K1] l_j'(x_i); at the nodes (samples = 0) the problem's own C table, dw[k][j] = C[j][k] '''
     if samples == 0:
         return np.array(spec.C, float).reshape(spec.K1, spec.K1).T.copy()
-    tau = np.asarray(spec.tau, float)
-    x = abscissae(spec, samples)
-    dw = np.zeros((len(x), spec.K1))
-    for i, xi in enumerate(x):
-        for j in range(spec.K1):
-            for m in range(spec.K1):
-                if m == j:
-                    continue
-                v = 1.0 / (tau[j] - tau[m])
-                for r in range(spec.K1):
-                    if r not in (j, m):
-                        v *= (xi - tau[r]) / (tau[j] - tau[r])
-                dw[i, j] += v
-    return dw
+    return lagrange_oracle.table(spec.tau, abscissae(spec, samples), lagrange_oracle.dbasis)
 
 
 def interpolate(spec, W, samples):

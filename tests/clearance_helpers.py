@@ -5,13 +5,12 @@ cases the CPU and the GPU tests share, their inputs, meshes and point sets.
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 
 from aircraft_trajectory_optimization_amd import native
 from tests import clearance_oracle
-from tests.helpers import REPO, product_spec
+from tests.helpers import REPO, build_twin, n_points, product_spec, rel_dev  # noqa: F401
 from tests.replay_helpers import MODELS, replay_inputs
 
 CLEAR_SRC = os.path.join(REPO, 'tests', 'native', 'clearance_hostcheck.cpp')
@@ -42,16 +41,7 @@ def case_id(c):
 
 
 def build_clearancecheck(force=False):
-    ''' the twin, with the g++ line of helpers.build_hostcheck '''
-    csrc = os.path.join(REPO, 'aircraft_trajectory_optimization_amd', 'csrc')
-    srcs = [CLEAR_SRC] + [os.path.join(csrc, f) for f in ('ato_models.hpp', 'ato_dual.hpp', 'ato_program.hpp',
-                                                         'ato_layout.hpp', 'ato_clearance.hpp', 'ato_mesh_pair.hpp')]
-    if not force and os.path.exists(CLEAR_LIB) and \
-            os.path.getmtime(CLEAR_LIB) >= max(os.path.getmtime(s) for s in srcs):
-        return CLEAR_LIB
-    subprocess.check_call(['g++', '-std=c++20', '-O3', '-march=x86-64-v3', '-fopenmp', '-fPIC', '-shared', '-o',
-                           CLEAR_LIB, CLEAR_SRC])
-    return CLEAR_LIB
+    return build_twin(CLEAR_SRC, CLEAR_LIB, ('ato_sample.hpp', 'ato_clearance.hpp', 'ato_mesh_pair.hpp'), force)
 
 
 @functools.lru_cache(maxsize=None)
@@ -70,10 +60,6 @@ def _lib():
     lib.atoc_mesh_sdist.argtypes = [vp, cl, vp, vp]
     lib.atoc_mesh_sdist_strided.argtypes = [vp, cl, vp, cl, cl, vp, ci, vp]
     return lib
-
-
-def n_points(spec, samples):
-    return spec.K1 if samples == 0 else samples + 1
 
 
 class ClearanceTwin:
@@ -203,12 +189,6 @@ def case_inputs(track, model, frame, K, B=3):
     for a in sets:
         a.setflags(write=False)
     return tuple(sets)
-
-
-def rel_dev(a, ref):
-    ''' largest deviation relative to max(1, |reference value|) '''
-    a, ref = np.asarray(a, float), np.asarray(ref, float)
-    return float(np.max(np.abs(a - ref) / np.maximum(1.0, np.abs(ref)), initial=0.0))
 
 
 # ------------------------------------------------------------------ meshes and point sets

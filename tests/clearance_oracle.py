@@ -1,12 +1,13 @@
 '''
-ORACLE (test infrastructure only) of the clearance: numpy restatement of the sample abscissae, the weight
-formula and the Lagrange sum, the product's own line.p2x for the lift (one call over all samples) and
+ORACLE (test infrastructure only) of the clearance: numpy restatement of the sample abscissae, the Lagrange
+basis (tests/lagrange_oracle.py) and the Lagrange sum, the product's own line.p2x for the lift (one call over all samples) and
 oracle.ref_mesh.signed_distance for the distance (another closest-point algorithm and another ray
 direction than the kernels).
 '''
 import numpy as np
 
 from oracle import ref_mesh
+from tests import lagrange_oracle
 
 
 def abscissae(spec, samples):
@@ -14,16 +15,8 @@ def abscissae(spec, samples):
 
 
 def weights(spec, samples):
-    ''' [S1][K1] l_j(x_i): the product over r != j, ascending, of (x - tau_r) / (tau_j - tau_r) '''
-    tau = np.asarray(spec.tau, float)
-    x = abscissae(spec, samples)
-    wt = np.ones((len(x), spec.K1))
-    for i, xi in enumerate(x):
-        for j in range(spec.K1):
-            for r in range(spec.K1):
-                if r != j:
-                    wt[i, j] *= (xi - tau[r]) / (tau[j] - tau[r])
-    return wt
+    ''' [S1][K1] l_j(x_i) '''
+    return lagrange_oracle.table(spec.tau, abscissae(spec, samples))
 
 
 def positions(spec, W, samples):

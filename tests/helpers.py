@@ -64,17 +64,35 @@ HOSTCHECK_SRC = os.path.join(REPO, 'tests', 'native', 'hostcheck.cpp')
 HOSTCHECK_LIB = os.path.join(REPO, 'tests', 'native', 'libato_hostcheck.so')
 
 
-def build_hostcheck(force=False):
-    srcs = [HOSTCHECK_SRC] + [os.path.join(REPO, 'aircraft_trajectory_optimization_amd', 'csrc', f)
-                              for f in ('ato_models.hpp', 'ato_dual.hpp', 'ato_program.hpp', 'ato_layout.hpp',
-                                        'ato_hessian.hpp')]
-    if not force and os.path.exists(HOSTCHECK_LIB) and \
-            os.path.getmtime(HOSTCHECK_LIB) >= max(os.path.getmtime(s) for s in srcs):
-        return HOSTCHECK_LIB
+BASE_HEADERS = ('ato_models.hpp', 'ato_dual.hpp', 'ato_program.hpp', 'ato_layout.hpp')
+
+
+def build_twin(src, lib, headers, force=False):
+    ''' g++ build of a test-only CPU twin (tests/native/*.cpp) of csrc headers; rebuilt when the source or one of
+    `headers` (names under csrc, next to BASE_HEADERS) is newer than the library '''
+    csrc = os.path.join(REPO, 'aircraft_trajectory_optimization_amd', 'csrc')
+    srcs = [src] + [os.path.join(csrc, f) for f in BASE_HEADERS + tuple(headers)]
+    if not force and os.path.exists(lib) and os.path.getmtime(lib) >= max(os.path.getmtime(s) for s in srcs):
+        return lib
     # x86-64-v3 (AVX2), not -march=native: the library is built here and also runs on the GPU box's host
     subprocess.check_call(['g++', '-std=c++20', '-O3', '-march=x86-64-v3', '-fopenmp', '-fPIC', '-shared', '-o',
-                           HOSTCHECK_LIB, HOSTCHECK_SRC])
-    return HOSTCHECK_LIB
+                           lib, src])
+    return lib
+
+
+def build_hostcheck(force=False):
+    return build_twin(HOSTCHECK_SRC, HOSTCHECK_LIB, ('ato_hessian.hpp',), force)
+
+
+def rel_dev(a, ref):
+    ''' largest deviation relative to max(1, |reference value|) '''
+    a, ref = np.asarray(a, float), np.asarray(ref, float)
+    return float(np.max(np.abs(a - ref) / np.maximum(1.0, np.abs(ref)), initial=0.0))
+
+
+def n_points(spec, samples):
+    ''' points per interval of the clearance and the audit (clearance_points, csrc/ato_sample.hpp) '''
+    return spec.K1 if samples == 0 else samples + 1
 
 
 class HostCheck:

@@ -1,7 +1,8 @@
 // audit_hostcheck.cpp -- TEST-ONLY CPU twin of the between-node audit kernel.
 //
 // Compiles csrc/ato_audit.hpp with g++ (no HIP) and runs the same audit_point() the kernel runs, one (instance,
-// interval, sample) at a time, with the same argument checks and weight tables. It is never loaded by the
+// interval, sample) of the kernel's own SampleGrid (csrc/ato_sample.hpp) at a time, with the same argument checks
+// and weight tables. It is never loaded by the
 // product package.
 #include <string>
 #include <vector>
@@ -38,15 +39,8 @@ void atoa_destroy(atoa_handle* h) { delete h; }
 
 int atoa_set_line(atoa_handle* h, const ato_line_table* t) {
     if (h->L.p.frame == ato::GLOBAL) return ATO_OK;
-    const size_t nx = (size_t)t->n_xc, nr = (size_t)t->n_ry;
-    std::vector<double>& b = h->line;
-    b.clear();
-    b.insert(b.end(), t->xc_knots, t->xc_knots + nx);
-    b.insert(b.end(), t->xc_coef, t->xc_coef + (nx + 1) * 12);
-    b.insert(b.end(), t->ry_knots, t->ry_knots + nr);
-    b.insert(b.end(), t->ry_coef, t->ry_coef + (nr + 1) * 12);
-    const double* d = b.data();
-    h->ld = ato::LineD{t->n_xc, t->n_ry, d, d + nx, d + nx + (nx + 1) * 12, d + nx + (nx + 1) * 12 + nr};
+    h->line = ato::line_pack(*t);
+    h->ld = ato::line_view(*t, h->line.data());
     return ATO_OK;
 }
 
@@ -83,23 +77,19 @@ int atoa_audit(const atoa_handle* h, int B, int layout, const double* w, int sam
         last_err = msg;
         return rc;
     }
-    const int S1 = ato::clearance_points(p.K1, samples);
-    std::vector<double> wt((size_t)S1 * p.K1), dw((size_t)S1 * p.K1);
+    const size_t len = (size_t)ato::clearance_points(p.K1, samples) * p.K1;
+    std::vector<double> wt(len), dw(len);
     ato::clearance_weights(p.tau, p.K1, samples, wt.data());
     ato::audit_dweights(p.tau, p.C, p.K1, samples, dw.data());
     const ato::AuditD a = ato::audit_args(p, samples, wt.data(), dw.data(), h->ld, lb, ub, bounds_per_instance);
-    const bool il = layout == ATO_LAYOUT_INTERLEAVED;
-    const long plane = (long)a.N * S1 * B;
+    const ato::SampleGrid g{a.N, a.S1, B, layout == ATO_LAYOUT_INTERLEAVED};
     ato::with_model(p, [&]<class M>() {
         for (int n = 0; n < a.N; ++n)
-            for (int i = 0; i < S1; ++i)
+            for (int i = 0; i < a.S1; ++i)
                 for (int b = 0; b < B; ++b) {
                     double out[ato::AUDIT_NCH];
-                    ato::audit_point<M>(a, n, i, b, B, il, w + (il ? (long)b : (long)b * a.nw), il ? (long)B : 1L, out);
-                    for (int c = 0; c < ato::AUDIT_NCH; ++c) {
-                        if (il) val[c * plane + ((long)n * S1 + i) * B + b] = out[c];
-                        else val[(((long)b * a.N + n) * S1 + i) * ato::AUDIT_NCH + c] = out[c];
-                    }
+                    ato::audit_point<M>(a, n, i, b, B, g.il, g.input(w, b, a.nw), g.stride(), out);
+                    g.store<ato::AUDIT_NCH>(val, n, i, b, out);
                 }
     });
     return ATO_OK;

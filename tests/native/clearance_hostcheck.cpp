@@ -1,8 +1,8 @@
 // clearance_hostcheck.cpp -- TEST-ONLY CPU twin of the clearance kernels.
 //
 // Compiles csrc/ato_clearance.hpp and csrc/ato_mesh_pair.hpp with g++ (no HIP) and runs the same
-// clearance_point() the position kernel runs, one (instance, interval, sample) at a time, with the same
-// argument checks and weight table; and the tiled signed distance over "waves" of 64 consecutive points with
+// clearance_point() the position kernel runs, one (instance, interval, sample) of the kernel's own SampleGrid
+// (csrc/ato_sample.hpp) at a time, with the same argument checks and weight table; and the tiled signed distance over "waves" of 64 consecutive points with
 // the kernel's own tiles (build_tiles), pair functions and decision functions (box_lb2, ray_meets_box). It is
 // never loaded by the product package.
 #include <string>
@@ -46,15 +46,8 @@ void atoc_destroy(atoc_handle* h) { delete h; }
 
 int atoc_set_line(atoc_handle* h, const ato_line_table* t) {
     if (h->L.p.frame == ato::GLOBAL) return ATO_OK;
-    const size_t nx = (size_t)t->n_xc, nr = (size_t)t->n_ry;
-    std::vector<double>& b = h->line;
-    b.clear();
-    b.insert(b.end(), t->xc_knots, t->xc_knots + nx);
-    b.insert(b.end(), t->xc_coef, t->xc_coef + (nx + 1) * 12);
-    b.insert(b.end(), t->ry_knots, t->ry_knots + nr);
-    b.insert(b.end(), t->ry_coef, t->ry_coef + (nr + 1) * 12);
-    const double* d = b.data();
-    h->ld = ato::LineD{t->n_xc, t->n_ry, d, d + nx, d + nx + (nx + 1) * 12, d + nx + (nx + 1) * 12 + nr};
+    h->line = ato::line_pack(*t);
+    h->ld = ato::line_view(*t, h->line.data());
     return ATO_OK;
 }
 
@@ -71,21 +64,16 @@ int atoc_clearance(const atoc_handle* h, int B, int layout, const double* w, int
         last_err = msg;
         return rc;
     }
-    const int S1 = ato::clearance_points(p.K1, samples);
-    std::vector<double> wt((size_t)S1 * p.K1);
+    std::vector<double> wt((size_t)ato::clearance_points(p.K1, samples) * p.K1);
     ato::clearance_weights(p.tau, p.K1, samples, wt.data());
     const ato::ClearD a = ato::clearance_args(p, samples, wt.data(), h->ld);
-    const bool il = layout == ATO_LAYOUT_INTERLEAVED;
-    const long plane = (long)a.N * S1 * B;
+    const ato::SampleGrid g{a.N, a.S1, B, layout == ATO_LAYOUT_INTERLEAVED};
     for (int n = 0; n < a.N; ++n)
-        for (int i = 0; i < S1; ++i)
+        for (int i = 0; i < a.S1; ++i)
             for (int b = 0; b < B; ++b) {
                 double out[3];
-                ato::clearance_point(a, n, i, w + (il ? (long)b : (long)b * a.nw), il ? (long)B : 1L, out);
-                for (int c = 0; c < 3; ++c) {
-                    if (il) pos[c * plane + ((long)n * S1 + i) * B + b] = out[c];
-                    else pos[(((long)b * a.N + n) * S1 + i) * 3 + c] = out[c];
-                }
+                ato::clearance_point(a, n, i, g.input(w, b, a.nw), g.stride(), out);
+                g.store<3>(pos, n, i, b, out);
             }
     return ATO_OK;
 }

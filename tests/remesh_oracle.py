@@ -1,18 +1,10 @@
 '''
-Test-side oracle of the mesh transfer (numpy): the product-formula weights and the triple loop of the
-definition in include/ato.h. Independent of csrc/ato_remesh.hpp: only the definition is shared.
+Test-side oracle of the mesh transfer (numpy): the Lagrange basis of tests/lagrange_oracle.py and the triple loop
+of the definition in include/ato.h. Independent of csrc/ato_remesh.hpp: only the definition is shared.
 '''
 import numpy as np
 
-
-def basis(tau, x):
-    ''' l_m(x), m = 0 .. K: product over q != m (ascending) of (x - tau_q) / (tau_m - tau_q) '''
-    out = np.ones(len(tau))
-    for m in range(len(tau)):
-        for q in range(len(tau)):
-            if q != m:
-                out[m] *= (x - tau[q]) / (tau[m] - tau[q])
-    return out
+from tests.lagrange_oracle import basis
 
 
 def weights(tau_s, tau_d, r):

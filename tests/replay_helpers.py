@@ -5,12 +5,11 @@ cases the CPU and the GPU tests share, and their inputs.
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 
 from aircraft_trajectory_optimization_amd import native
-from tests.helpers import REPO, product_spec, random_w
+from tests.helpers import REPO, build_twin, product_spec, random_w, rel_dev  # noqa: F401
 
 REPLAY_SRC = os.path.join(REPO, 'tests', 'native', 'replay_hostcheck.cpp')
 REPLAY_LIB = os.path.join(REPO, 'tests', 'native', 'libato_replaycheck.so')
@@ -37,16 +36,7 @@ def case_id(c):
 
 
 def build_replaycheck(force=False):
-    ''' the twin, with the g++ line of helpers.build_hostcheck '''
-    csrc = os.path.join(REPO, 'aircraft_trajectory_optimization_amd', 'csrc')
-    srcs = [REPLAY_SRC] + [os.path.join(csrc, f) for f in ('ato_models.hpp', 'ato_dual.hpp', 'ato_program.hpp',
-                                                          'ato_layout.hpp', 'ato_replay.hpp')]
-    if not force and os.path.exists(REPLAY_LIB) and \
-            os.path.getmtime(REPLAY_LIB) >= max(os.path.getmtime(s) for s in srcs):
-        return REPLAY_LIB
-    subprocess.check_call(['g++', '-std=c++20', '-O3', '-march=x86-64-v3', '-fopenmp', '-fPIC', '-shared', '-o',
-                           REPLAY_LIB, REPLAY_SRC])
-    return REPLAY_LIB
+    return build_twin(REPLAY_SRC, REPLAY_LIB, ('ato_sample.hpp', 'ato_replay.hpp'), force)
 
 
 class ReplayTwin:
@@ -123,9 +113,3 @@ def replay_inputs(spec, B, seed=0):
     W = np.stack([random_w(spec, rng) for _ in range(B)])
     W[:, :spec.N] = 0.05 + 0.25 * rng.random((B, spec.N))
     return W
-
-
-def rel_dev(a, ref):
-    ''' largest deviation relative to max(1, |reference value|) '''
-    a, ref = np.asarray(a, float), np.asarray(ref, float)
-    return float(np.max(np.abs(a - ref) / np.maximum(1.0, np.abs(ref)), initial=0.0))

@@ -1,26 +1,17 @@
 '''
 Test-side oracle of the replay (numpy): classical RK4 over oracle.ref_models with frame='global',
-the Lagrange-weight formula of the library, lifting through the Python centreline. Independent of
+the Lagrange basis of tests/lagrange_oracle.py, lifting through the Python centreline. Independent of
 csrc/ato_replay.hpp: only the definition in include/ato.h is shared.
 '''
 import numpy as np
 
 from oracle import ref_models
+from tests import lagrange_oracle
 
 
 def weights(tau, S):
-    ''' l_j(i / (2 S)), i = 0 .. 2 S: product over r != j (ascending) of (x - tau_r) / (tau_j - tau_r) '''
-    K1 = len(tau)
-    lw = np.zeros((2 * S + 1, K1))
-    for i in range(2 * S + 1):
-        x = float(i) / float(2 * S)
-        for j in range(K1):
-            v = 1.0
-            for r in range(K1):
-                if r != j:
-                    v *= (x - tau[r]) / (tau[j] - tau[r])
-            lw[i, j] = v
-    return lw
+    ''' l_j(i / (2 S)), i = 0 .. 2 S '''
+    return lagrange_oracle.table(tau, [float(i) / float(2 * S) for i in range(2 * S + 1)])
 
 
 def _veh(spec):

@@ -2,7 +2,7 @@
 Build libato.so for gfx950 in-tree (aircraft_trajectory_optimization_amd/_lib/).
 
 One object per model variant (ato_inst.hip, -DATO_INST=i) plus the C-ABI object, compiled
-in parallel with hipcc, the replay kernels (ato_replay.hip), the mesh-transfer kernel (ato_remesh.hip), the clearance kernel (ato_clearance.hip), the audit kernel (ato_audit.hip), and the host-only Hessian structure analysis (ato_hstruct.cpp, g++),
+in parallel with hipcc, the replay kernels (ato_replay.hip), the mesh-transfer kernel (ato_remesh.hip), the clearance kernel (ato_clearance.hip), the audit kernel (ato_audit.hip), the gate-passage kernels (ato_gatecheck.hip), and the host-only Hessian structure analysis (ato_hstruct.cpp, g++),
 then linked into a shared library. Objects are rebuilt only when
 a source or header is newer (every csrc/*.hpp counts, ato_sample.hpp, the layer the four post-solve kernels share,
 included).
@@ -63,6 +63,7 @@ def build(verbose=True, jobs=None) -> str:
             (os.path.join(CSRC, 'ato_remesh.hip'), os.path.join(OBJ, 'ato_remesh.o'), []),
             (os.path.join(CSRC, 'ato_clearance.hip'), os.path.join(OBJ, 'ato_clearance.o'), []),
             (os.path.join(CSRC, 'ato_audit.hip'), os.path.join(OBJ, 'ato_audit.o'), []),
+            (os.path.join(CSRC, 'ato_gatecheck.hip'), os.path.join(OBJ, 'ato_gatecheck.o'), []),
             # no contraction: the interior-point column kernels reproduce the host formulas bit for bit
             (os.path.join(CSRC, 'ato_ipm.hip'), os.path.join(OBJ, 'ato_ipm.o'), ['-ffp-contract=off'])]
     for i in range(N_INST):

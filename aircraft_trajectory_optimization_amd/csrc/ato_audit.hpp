@@ -34,7 +34,7 @@
 // [NV][B], instance-major [B][NV]); NULL gives +inf in channels 0-5, an infinite bound contributes +inf.
 //
 // NOT covered: the obstacle-tube sphere rows (a per-node table with no definition between nodes; the clearance
-// answers that on the mesh itself), gates and closure rows (point constraints), CPC progress variables (not
+// answers that on the mesh itself), gates (ato_gatecheck.hpp) and closure rows (point constraints), CPC progress variables (not
 // read), the dU rows (a degree-K interpolant that matches another's derivative at K + 1 points is that
 // derivative everywhere) and RK4 transcriptions. The audit bounds nothing about the arc between two samples.
 //

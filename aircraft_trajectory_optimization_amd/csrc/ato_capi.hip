@@ -58,6 +58,8 @@ static void release(ato_handle* h) {
     for (auto& kv : h->remesh_tabs) (void)hipFree(kv.second.dev);
     (void)hipFree(h->d_line);
     (void)hipFree(h->d_clear_pos);
+    (void)hipFree(h->d_gate_tau);       // the planes follow tau in the same allocation
+    (void)hipFree(h->d_gate_part);
     for (ato_weight_cache* c : {&h->replay_w, &h->clear_w, &h->audit_w}) (void)hipFree(c->dev);
     h->remesh_tabs.clear();
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
@@ -147,6 +149,27 @@ static int create_impl(const ato_problem_desc* desc, ato_handle** out) {
             delete h;
             return fail(ATO_ERR_HIP, c.what);
         }
+    // gate passage: tau and room for GATE_MAX planes, the problem's own gates uploaded (a problem with more than
+    // GATE_MAX keeps its count, which ato_gatecheck rejects)
+    {
+        const size_t tau_bytes = (ATO_KMAX + 1) * sizeof(double);
+        if (hipMalloc((void**)&h->d_gate_tau, tau_bytes + ato::GATE_MAX * sizeof(ato_gate_plane)) != hipSuccess) {
+            release(h);
+            delete h;
+            return fail(ATO_ERR_HIP, "gate planes: out of device memory");
+        }
+        h->d_gate_planes = (ato_gate_plane*)(h->d_gate_tau + ATO_KMAX + 1);
+        const std::vector<ato_gate_plane> own = ato::gate_planes_of(h->L.gates);
+        h->n_gate_planes = (int32_t)own.size();
+        hipError_t e = hipMemcpy(h->d_gate_tau, h->L.p.tau, tau_bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !own.empty() && own.size() <= (size_t)ato::GATE_MAX)
+            e = hipMemcpy(h->d_gate_planes, own.data(), own.size() * sizeof(ato_gate_plane), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            release(h);
+            delete h;
+            return fail(ATO_ERR_HIP, "gate planes: upload failed");
+        }
+    }
     h->pd = h->L.p;
     h->pd.geom = h->d_geom;
     h->pd.node_s = h->d_node_s;
@@ -591,6 +614,82 @@ static int audit_impl(ato_handle* h, int32_t batch, int32_t layout, const double
 extern "C" int ato_audit(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t samples,
                          const double* lb, const double* ub, int32_t bounds_per_instance, double* val, void* stream) {
     ATO_NOEXCEPT_BODY(audit_impl(h, batch, layout, w, samples, lb, ub, bounds_per_instance, val, stream))
+}
+
+static int gatecheck_set_gates_impl(ato_handle* h, const ato_gate_plane* planes, int32_t n) {
+    if (!h) return fail(ATO_ERR_ARG, "null handle");
+    if (n < 0 || n > ato::GATE_MAX) return fail(ATO_ERR_ARG, "gate planes: n must be in [0, 64]");
+    if (n > 0 && !planes) return fail(ATO_ERR_ARG, "null argument");
+    std::vector<ato_gate_plane> use = n > 0 ? std::vector<ato_gate_plane>(planes, planes + n)
+                                            : ato::gate_planes_of(h->L.gates);
+    for (const ato_gate_plane& g : use)
+        if (g.shape != ATO_GATE_CIRCLE && g.shape != ATO_GATE_SQUARE) return fail(ATO_ERR_ARG, "bad gate shape");
+    ATO_HIP(hipDeviceSynchronize());      // a queued gate check may still read the planes these replace
+    if (!use.empty() && use.size() <= (size_t)ato::GATE_MAX)
+        ATO_HIP(hipMemcpy(h->d_gate_planes, use.data(), use.size() * sizeof(ato_gate_plane), hipMemcpyHostToDevice));
+    h->n_gate_planes = (int32_t)use.size();
+    h->gate_last[0] = -1;      // the records on the handle belong to other planes
+    return ATO_OK;
+}
+
+extern "C" int ato_gatecheck_set_gates(ato_handle* h, const ato_gate_plane* planes, int32_t n) {
+    ATO_NOEXCEPT_BODY(gatecheck_set_gates_impl(h, planes, n))
+}
+
+// grow a buffer of the handle to len doubles; hipFree waits for the work that still reads the old one
+static int grow(double** buf, size_t* have, size_t len, const char* what) {
+    if (*have >= len) return ATO_OK;
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *have = 0;
+    if (hipMalloc((void**)buf, len * sizeof(double)) != hipSuccess) return fail(ATO_ERR_HIP, what);
+    *have = len;
+    return ATO_OK;
+}
+
+static int gatecheck_impl(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t samples,
+                          double axial_tol, double* val, void* stream, int32_t launches) {
+    if (!h) return fail(ATO_ERR_ARG, "null handle");
+    const ato::ProbD& p = h->pd;
+    const char* msg = "";
+    if (int rc = ato::gatecheck_check(p, h->d_line != nullptr, h->n_gate_planes, batch, layout, samples, axial_tol,
+                                      &msg))
+        return fail(rc, msg);
+    if (!w || !val) return fail(ATO_ERR_ARG, "null buffer");
+    if (launches < 1 || launches > 7) return fail(ATO_ERR_ARG, "launches must be in [1, 7]");
+    hipStream_t st = (hipStream_t)stream;
+    const int G = h->n_gate_planes, S1 = samples + 1;
+    // a subset of the launches reads what a whole call left in the handle's buffers: only after one of this shape
+    const int64_t shape[4] = {batch, layout, samples, G};
+    if (launches != 7 && !std::equal(shape, shape + 4, h->gate_last))
+        return fail(ATO_ERR_STATE, "a subset of the launches needs a whole ato_gatecheck call of the same shape before it");
+    if (int rc = grow(&h->d_clear_pos, &h->clear_pos_len, (size_t)3 * p.N * S1 * batch,
+                      "gate passage positions: out of device memory"))
+        return rc;
+    if (int rc = grow(&h->d_gate_part, &h->gate_part_len, (size_t)G * p.N * ato::GATE_PART * batch,
+                      "gate passage records: out of device memory"))
+        return rc;
+    ATO_HIP(h->clear_w.use(samples, (size_t)S1 * p.K1,
+                           [&](double* wt) { ato::clearance_weights(p.tau, p.K1, samples, wt); }, st));
+    const ato::GateD a =
+        ato::gatecheck_args(p, samples, h->clear_w.dev, h->line, h->d_gate_tau, h->d_gate_planes, G, axial_tol);
+    hipError_t e = hipSuccess;
+    if (launches & 1) e = ato::launch_clearance_pos(a.c, batch, layout, w, h->d_clear_pos, st);
+    if (e == hipSuccess && (launches & 6))
+        e = ato::launch_gatecheck(a, batch, layout, w, h->d_clear_pos, h->d_gate_part, val, st, launches >> 1);
+    if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("gate passage launch: ") + hipGetErrorString(e));
+    if (launches == 7) std::copy(shape, shape + 4, h->gate_last);
+    return ATO_OK;
+}
+
+extern "C" int ato_gatecheck(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t samples,
+                             double axial_tol, double* val, void* stream) {
+    ATO_NOEXCEPT_BODY(gatecheck_impl(h, batch, layout, w, samples, axial_tol, val, stream, 7))
+}
+
+extern "C" int ato_gatecheck_launches(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t samples,
+                                      double axial_tol, double* val, void* stream, int32_t launches) {
+    ATO_NOEXCEPT_BODY(gatecheck_impl(h, batch, layout, w, samples, axial_tol, val, stream, launches))
 }
 
 extern "C" int ato_eval(ato_handle* h, int32_t batch, int32_t layout, const double* w, double* g,

@@ -8,6 +8,7 @@
 #include "ato_remesh.hpp"
 #include "ato_clearance.hpp"
 #include "ato_audit.hpp"
+#include "ato_gatecheck.hpp"
 
 // A Lagrange weight table on the device, keyed by a substep or sample count. dev is allocated once (ato_create,
 // sized for the largest key) and holds the table of the key last uploaded; the host tables it is uploaded from
@@ -96,4 +97,13 @@ struct ato_handle {
     size_t clear_pos_len = 0;
     // audit (ato_audit.hpp): value and derivative weight tables by sample count, back to back
     ato_weight_cache audit_w;
+    // gate passage (ato_gatecheck.hpp): tau_0 .. tau_K and up to GATE_MAX planes in one allocation (ato_create),
+    // the planes in use (the problem's own unless ato_gatecheck_set_gates replaced them) and the partial records
+    // [G][N][GATE_PART][B] (grown only when a call needs more). Positions: d_clear_pos and clear_w above.
+    double* d_gate_tau = nullptr;
+    ato_gate_plane* d_gate_planes = nullptr;
+    int32_t n_gate_planes = 0;
+    double* d_gate_part = nullptr;
+    size_t gate_part_len = 0;
+    int64_t gate_last[4] = {-1, -1, -1, -1};   // batch, layout, samples, G of the last whole call (ato_gatecheck_launches)
 };

@@ -1,4 +1,5 @@
-// ato_sample.hpp -- the sampling layer the post-solve checks share (replay, mesh transfer, clearance, audit).
+// ato_sample.hpp -- the sampling layer the post-solve checks share (replay, mesh transfer, clearance, audit,
+// gate passage).
 //
 // Each of them evaluates an interval's collocation polynomial away from its nodes and, in parametric problems,
 // places the result through the centreline. What they have in common lives here, once:
@@ -27,16 +28,20 @@ namespace ato {
 constexpr int SAMPLE_SMAX = 64;
 
 // ---------------------------------------------------------------- Lagrange basis (host side, fp64)
-// l_j(x), j = 0 .. K1 - 1: the product over r != j (ascending) of (x - tau_r) / (tau_j - tau_r)
-inline void lagrange_row(const double* tau, int K1, double x, double* l) {
-    for (int j = 0; j < K1; ++j) {
-        double v = 1.0;
-        for (int r = 0; r < K1; ++r) {
-            if (r == j) continue;
-            v *= (x - tau[r]) / (tau[j] - tau[r]);
-        }
-        l[j] = v;
+// l_j(x): the product over r != j (ascending) of (x - tau_r) / (tau_j - tau_r). ATO_HD: the gate check evaluates
+// it on the device at bisection midpoints, one weight at a time (no row array in registers)
+ATO_HD double lagrange_weight(const double* tau, int K1, double x, int j) {
+    double v = 1.0;
+    for (int r = 0; r < K1; ++r) {
+        if (r == j) continue;
+        v *= (x - tau[r]) / (tau[j] - tau[r]);
     }
+    return v;
+}
+
+// l_j(x), j = 0 .. K1 - 1
+ATO_HD void lagrange_row(const double* tau, int K1, double x, double* l) {
+    for (int j = 0; j < K1; ++j) l[j] = lagrange_weight(tau, K1, x, j);
 }
 
 // l_j'(x) = sum_{m != j} 1 / (tau_j - tau_m) prod_{r != j, m} (x - tau_r) / (tau_j - tau_r), m and r ascending
@@ -204,6 +209,19 @@ struct SampleGrid {
     // element 0 of instance b's decision vector (length nw) and its element stride
     ATO_HD const double* input(const double* w, int b, int nw) const { return w + (il ? (long)b : (long)b * nw); }
     ATO_HD long stride() const { return il ? (long)B : 1L; }
+    // the NCH channels of item (n, i, b) of a buffer a store<NCH> filled
+    template <int NCH>
+    ATO_HD void load(const double* in, int n, int i, int b, double* v) const {
+        if (il) {
+            const long plane = (long)N * S1 * B, p = (long)(n * S1 + i) * B + b;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) v[c] = in[c * plane + p];
+        } else {
+            const long p = ((long)b * N + n) * S1 + i;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) v[c] = in[p * NCH + c];
+        }
+    }
     template <int NCH>
     ATO_HD void store(double* out, int n, int i, int b, const double* v) const {
         if (il) {

@@ -20,6 +20,8 @@ ATO_TRANS_COLLOCATION, ATO_TRANS_RK4 = 0, 1
 ATO_GATE_CIRCLE, ATO_GATE_SQUARE = 0, 1
 ATO_LAYOUT_INTERLEAVED, ATO_LAYOUT_INSTANCE_MAJOR = 0, 1
 ATO_AUDIT_NCH = 14      # channels per item of ato_audit
+ATO_GATECHECK_NCH = 9   # channels per (gate, instance) of ato_gatecheck
+GATE_MAX = 64           # gates per ato_gatecheck call
 ATO_OK, ATO_ERR_ARG, ATO_ERR_UNSUPPORTED, ATO_ERR_HIP, ATO_ERR_STATE = 0, -1, -2, -3, -4
 ABI_VERSION = 3
 CPC_MAX = 16                 # ATO_CPC_MAX
@@ -110,6 +112,28 @@ def line_table_struct(table: dict):
     return t, keep
 
 
+class AtoGatePlane(ctypes.Structure):
+    ''' mirror of ato_gate_plane '''
+    _fields_ = [('centre', ctypes.c_double * 3), ('R', ctypes.c_double * 9), ('d_max', ctypes.c_double),
+                ('shape', ctypes.c_int32), ('pad', ctypes.c_int32)]
+
+
+def gate_plane_array(planes: dict):
+    ''' ctypes array of AtoGatePlane from {'centre' (G, 3), 'R' (G, 3, 3), 'd_max' (G,), 'shape' (G,)} '''
+    c = np.asarray(planes['centre'], np.float64).reshape(-1, 3)
+    G = len(c)
+    R = np.asarray(planes['R'], np.float64).reshape(G, 9)
+    d = np.asarray(planes['d_max'], np.float64).reshape(G)
+    sh = np.asarray(planes['shape']).reshape(G)
+    arr = (AtoGatePlane * max(G, 1))()
+    for i in range(G):
+        arr[i].centre[:] = c[i].tolist()
+        arr[i].R[:] = R[i].tolist()
+        arr[i].d_max = float(d[i])
+        arr[i].shape = int(sh[i])
+    return arr, G
+
+
 class AtoIpmDims(ctypes.Structure):
     ''' include/ato_ipm.h ato_ipm_dims '''
     _fields_ = [('n', ctypes.c_int32), ('m', ctypes.c_int32), ('mi', ctypes.c_int32), ('meq', ctypes.c_int32),
@@ -136,7 +160,8 @@ EXPORTED_SYMBOLS = ('ato_create', 'ato_destroy', 'ato_sizes', 'ato_sparsity', 'a
                     'ato_kkt_residual', 'ato_kkt_residual_list', 'ato_set_instance_spheres',
                     'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity', 'ato_replay_set_lift',
                     'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided', 'ato_clearance_set_line',
-                    'ato_clearance', 'ato_audit') + IPM_SYMBOLS
+                    'ato_clearance', 'ato_audit', 'ato_gatecheck', 'ato_gatecheck_set_gates',
+                    'ato_gatecheck_launches') + IPM_SYMBOLS
 
 
 def library_path() -> str:
@@ -181,6 +206,9 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
         lib.ato_clearance.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp,
                                       ctypes.c_int32, vp]
         lib.ato_audit.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp]
+        lib.ato_gatecheck.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_double, vp, vp]
+        lib.ato_gatecheck_launches.argtypes = lib.ato_gatecheck.argtypes + [ctypes.c_int32]
+        lib.ato_gatecheck_set_gates.argtypes = [vp, ctypes.POINTER(AtoGatePlane), ctypes.c_int32]
         lib.ato_kkt_create.argtypes = [vp, ctypes.POINTER(vp)]
         lib.ato_kkt_destroy.argtypes = [vp]
         lib.ato_kkt_reserve.argtypes = [vp, ctypes.c_int32]
@@ -226,7 +254,8 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
                    'ato_timing_read', 'ato_timing_stride', 'ato_mesh_create', 'ato_mesh_destroy', 'ato_mesh_signed_distance',
                    'ato_set_instance_spheres', 'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity',
                    'ato_replay_set_lift', 'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided',
-                   'ato_clearance_set_line', 'ato_clearance', 'ato_audit'):
+                   'ato_clearance_set_line', 'ato_clearance', 'ato_audit', 'ato_gatecheck',
+                   'ato_gatecheck_set_gates', 'ato_gatecheck_launches'):
             getattr(lib, fn).restype = ctypes.c_int
     return lib
 
@@ -514,6 +543,36 @@ class NativeProblem:
         NotImplementedError with the library's message.
         '''
         rc = self.audit_rc(batch, w, samples, val, lb, ub, bounds_per_instance, layout, stream)
+        self._check_supported(rc)
+
+    def gatecheck_set_gates(self, planes: Optional[dict]):
+        ''' replace the gates ato_gatecheck checks: gate_plane_array's dict, copied; None: the problem's own '''
+        if planes is None:
+            self._check(self.lib.ato_gatecheck_set_gates(self.handle, None, 0))
+            return
+        arr, G = gate_plane_array(planes)
+        if G < 1:
+            raise ValueError('no gate planes given (None returns to the problem\'s own)')
+        self._check(self.lib.ato_gatecheck_set_gates(self.handle, arr, G))
+
+    def gatecheck_rc(self, batch: int, w: int, samples: int, val: int, axial_tol: float = 1e-6,
+                     layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0, launches: int = 7) -> int:
+        ''' ato_gatecheck on device pointers; returns the library's code (ato_last_error has the message).
+        launches: bit mask of the launches to run (ato_gatecheck_launches; timing only) '''
+        if launches != 7:
+            return self.lib.ato_gatecheck_launches(self.handle, int(batch), int(layout), w or None, int(samples),
+                                                   float(axial_tol), val or None, stream or None, int(launches))
+        return self.lib.ato_gatecheck(self.handle, int(batch), int(layout), w or None, int(samples),
+                                      float(axial_tol), val or None, stream or None)
+
+    def gatecheck_ptrs(self, batch: int, w: int, samples: int, val: int, axial_tol: float = 1e-6,
+                       layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0):
+        '''
+        Gate passage of the decision vectors w (asynchronous on `stream`; include/ato.h ato_gatecheck): samples in
+        [1, 64], val [ATO_GATECHECK_NCH x G x batch] (interleaved) or [batch x G x ATO_GATECHECK_NCH].
+        RK4-transcribed problems raise NotImplementedError with the library's message.
+        '''
+        rc = self.gatecheck_rc(batch, w, samples, val, axial_tol, layout, stream)
         self._check_supported(rc)
 
     def timing_start(self, max_calls: int):

@@ -11,7 +11,8 @@ model variant (the relative attitude included, which the replay does not cover),
 the sample's own s rather than frozen at the node's nominal s as the NLP does.
 
 What it does not look at: the obstacle-tube sphere rows (a per-node table; the clearance answers that on the
-mesh), gates and closure rows (point constraints), CPC progress variables, the dU rows (exact between the
+mesh), gates (raceline/gates.py asks the continuous trajectory about them) and closure rows (point constraints),
+CPC progress variables, the dU rows (exact between the
 nodes when they hold at them) and RK4 transcriptions. It says nothing about the arc between two samples: there
 is no Lipschitz argument here as there is for distances. No solver path calls it.
 '''

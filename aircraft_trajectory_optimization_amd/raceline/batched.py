@@ -49,6 +49,7 @@ class BatchedNLP:
         self.row_ptr, self.col = self.problem.sparsity()
         self.lbg, self.ubg = self.problem.bounds()
         self.isph = None          # per-instance sphere centres [2 P][B] (set_instance_spheres)
+        self._n_planes = None     # gates given to set_gates (None: the problem's own, len(spec.gates))
 
     def set_instance_spheres(self, tables: Optional[np.ndarray]):
         '''
@@ -252,6 +253,39 @@ class BatchedNLP:
         self.problem.audit_ptrs(B, W.data_ptr(), S, val.data_ptr(), lb.data_ptr() if lb is not None else 0,
                                 ub.data_ptr() if ub is not None else 0, per, layout=self.layout,
                                 stream=st.cuda_stream)
+        return val
+
+    def set_gates(self, planes: Optional[dict]):
+        ''' the gates gatecheck() checks: {'centre' (G, 3), 'R' (G, 3, 3), 'd_max' (G,), 'shape' (G,)} as
+        raceline.gates.gate_planes returns them (at most 64, copied); None: the problem's own '''
+        with torch.cuda.device(self.device):
+            self.problem.gatecheck_set_gates(planes)
+        self._n_planes = None if planes is None else len(np.asarray(planes['d_max']).reshape(-1))
+
+    def gatecheck(self, W=None, samples: int = 16, axial_tol: float = 1e-6, stream=None) -> torch.Tensor:
+        '''
+        Passage of the continuous trajectory through every gate's opening (ato_gatecheck, asynchronous on
+        `stream`): sign changes of the axial coordinate between the S + 1 points of every interval at
+        i / samples (samples in [1, 64]), refined by bisection of the collocation polynomial, parametric
+        problems placed through the centreline at the point's own s. W as in audit(). axial_tol (m): on open
+        lines the first and the last point count as crossings within it. The gates are the problem's own unless
+        set_gates() replaced them. Returns val in the layout: interleaved (NCH, G, B), instance-major (B, G, NCH);
+        the channels (n_cross, margin, interval, x, t, p2, p3, off, flag) are listed in include/ato.h. One
+        stream per problem handle: the weight table and the position buffer are handle state. RK4-transcribed
+        problems raise NotImplementedError; a problem without gates raises RuntimeError.
+        '''
+        B = self.batch
+        il = self.layout == native.ATO_LAYOUT_INTERLEAVED
+        W = self._columns(W, 'gatecheck')
+        self._ensure_line()
+        G = len(self.spec.gates) if self._n_planes is None else self._n_planes
+        nch = native.ATO_GATECHECK_NCH
+        val = torch.empty((nch, G, B) if il else (B, G, nch), device=self.device, dtype=torch.float64)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if stream is not None:      # a temporary made on the current stream, read on another
+            W.record_stream(st)
+        self.problem.gatecheck_ptrs(B, W.data_ptr(), int(samples), val.data_ptr(), float(axial_tol),
+                                    layout=self.layout, stream=st.cuda_stream)
         return val
 
     def remesh_from(self, src: 'BatchedNLP', W_src, cols=None, stream=None) -> torch.Tensor:

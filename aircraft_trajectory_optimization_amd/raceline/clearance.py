@@ -10,8 +10,8 @@ their signed distance to the mesh through the tiled kernel), or, with flown=True
 ODE actually flies under the solution's inputs (the replay's dense trajectory) is.
 
 It certifies positions against the mesh. Variable bounds, s' >= 0 and the ODE defects between the nodes are the
-audit's (raceline/audit.py); nothing checks gates there, and between two samples only the chord bound below
-holds.
+audit's (raceline/audit.py) and the gates' openings the gate check's (raceline/gates.py); between two samples only
+the chord bound below holds.
 '''
 from dataclasses import dataclass
 from typing import Optional

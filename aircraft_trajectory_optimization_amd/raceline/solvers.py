@@ -147,6 +147,17 @@ class _Raceline:
         from aircraft_trajectory_optimization_amd.raceline.audit import audit_solutions
         return audit_solutions(self.spec, self._solution_vector(results)[None], samples=samples, varying='outer')
 
+    def gate_passage(self, results=None, samples: int = 16, tol: float = 0.0):
+        '''
+        Passage of a solution of this problem through its gates on the device (raceline/gates.py): where and when
+        the continuous trajectory crosses each gate's plane and how far inside the opening. `results` is a
+        RacelineResults of solve() (default: the last one) or a decision vector. Returns the GatePassageResult
+        of that one instance. RK4 transcriptions raise NotImplementedError, a problem without gates (a
+        parametric line without gate_s, a CPC problem) RuntimeError.
+        '''
+        from aircraft_trajectory_optimization_amd.raceline.gates import gate_passage
+        return gate_passage(self.spec, self._solution_vector(results)[None], samples=samples, tol=tol)
+
     def _solution_vector(self, results_or_x=None) -> np.ndarray:
         ''' the decision vector of a RacelineResults of solve() (default: the last one), or the vector itself '''
         if results_or_x is None or isinstance(results_or_x, RacelineResults):

@@ -260,8 +260,8 @@ int ato_remesh(ato_handle* src, ato_handle* dst, int32_t batch_src, int32_t batc
  * sample's own interpolated s, from the centreline's two piecewise cubics: knots [n] and coefficients
  * [n + 1][4][3] (piece, power 0..3, axis) of x_c and of r_y, piece 0 left of the first knot and piece n right of
  * the last (linear extrapolation), the piece of s being the number of knots <= s. Host arrays, copied; not needed
- * (ignored) for global-frame problems. It certifies positions against the mesh, nothing about gates or the arc
- * between samples; variable bounds and s' >= 0 between the nodes are ato_audit's. */
+ * (ignored) for global-frame problems. It certifies positions against the mesh, nothing about the arc between
+ * samples; variable bounds and s' >= 0 between the nodes are ato_audit's, gate openings ato_gatecheck's. */
 typedef struct ato_line_table {
     int32_t n_xc, n_ry;
     const double *xc_knots, *xc_coef, *ry_knots, *ry_coef;
@@ -295,7 +295,7 @@ int ato_clearance(ato_handle* h, ato_mesh* mesh, int32_t batch, int32_t layout, 
  * lb, ub: device bounds per component of the node vector, [NV], or with bounds_per_instance [NV x batch] in
  * `layout`; both NULL: +inf in channels 0-5. val: item p, channel c at [c * N*S1*batch + p] with
  * p = (n S1 + i) batch + b (interleaved) or at [p * ATO_AUDIT_NCH + c] with p = (b N + n) S1 + i
- * (instance-major). Not covered: obstacle-tube sphere rows, gates and closure rows, CPC variables, the dU rows,
+ * (instance-major). Not covered: obstacle-tube sphere rows, gates (ato_gatecheck), closure rows, CPC variables, the dU rows,
  * RK4 transcriptions, and the arc between two samples. Asynchronous on stream; no device-wide synchronisation;
  * both weight tables are uploaded on the stream when samples changes. The tables are per-handle state: use ONE
  * stream per handle for ato_audit (and likewise for ato_clearance and ato_replay), or synchronise between calls
@@ -306,6 +306,62 @@ int ato_clearance(ato_handle* h, ato_mesh* mesh, int32_t batch, int32_t layout, 
 #define ATO_AUDIT_NCH 14
 int ato_audit(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t samples, const double* lb,
               const double* ub, int32_t bounds_per_instance, double* val, void* stream);
+
+/* Gate passage of collocation solutions (csrc/ato_gatecheck.hpp): does the continuous trajectory go through each
+ * gate's opening, where and when. A gate plane has a centre c, axes e1 e2 e3 (the columns of R, row-major as in
+ * ato_gate), a half-opening d_max and a shape; a point at global position x has a = e1.(x - c), p2 = e2.(x - c),
+ * p3 = e3.(x - c). The points of a lap are the samples of ato_clearance, (n, i) at abscissa i / S, i = 0 .. S,
+ * n = 0 .. N - 1 (samples = S in [1, 64]; the node rule samples = 0 is rejected: it leaves the tail (tau_K, 1]
+ * without a bracket), parametric problems placed through the centreline at the point's own s; closed problems wrap
+ * to (0, 0). A crossing lies between consecutive points whose (a >= 0) differ: inside one interval it is refined by
+ * 53 bisections of the polynomial itself and reported at the right end of the last bracket; across an interval
+ * junction or the wrap it is the later point, unrefined. On open lines the first and the last point are crossings
+ * too when |a| <= axial_tol (metres; their gates sit on them). The margin of a crossing is d_max - sqrt(p2^2 + p3^2)
+ * (circle) or d_max - max(|p2|, |p3|) (square), fix_center gates included (their exact row is channel 7). The
+ * direction of a crossing is recorded, not required. Per (gate, instance) ATO_GATECHECK_NCH doubles:
+ *   0  n_cross   crossings found
+ *   1  margin    of the best crossing (the largest margin, ties to the earliest (n, x)); -inf if there is none
+ *   2  interval  n of the best crossing (-1: none)
+ *   3  x         its abscissa in [0, 1]
+ *   4  t         sum_{m < n} h_m + x h_n, the passage time
+ *   5, 6  p2, p3 lateral offsets there
+ *   7  off       sqrt(p2^2 + p3^2)
+ *   8  flag      +1 / -1: direction of the best crossing along e1; 0: none; NaN: some evaluated a or margin of
+ *                this (gate, instance) was not finite (a non-finite value never becomes the best crossing), or
+ *                some step size h_n is not finite and positive
+ * Channels 3-7 are NaN without a crossing. val: channel c of gate g, instance b at [(c G + g) batch + b]
+ * (interleaved) or [(b G + g) ATO_GATECHECK_NCH + c] (instance-major). The gates are the problem's own (centre, R,
+ * d_max, shape of desc.gates, in their order) unless ato_gatecheck_set_gates replaced them: planes is a host array
+ * of n <= 64 planes, copied (tighter openings, CPC waypoints as circular gates); n = 0 returns to the problem's
+ * own. It reads the first three state components only: any model, any attitude, the three frames. Not covered: the
+ * trajectory as flown (ato_replay), RK4 transcriptions, closure rows, the gate's frame as an obstacle, gate order
+ * (t is reported). Three launches on the stream (positions, crossings per interval, reduction per gate); no
+ * device-wide synchronisation, no atomics: bitwise repeatable, independent of the batch. The partial records live
+ * in a buffer on the handle, grown only when a call needs more. The weight table and the position buffer are
+ * per-handle state shared with ato_clearance: use ONE stream per handle for ato_gatecheck, ato_clearance, ato_audit
+ * and ato_replay, or synchronise between calls on different streams. ATO_ERR_UNSUPPORTED: RK4 transcription;
+ * ATO_ERR_STATE: a parametric problem without its centreline table (ato_clearance_set_line), or no gates (a CPC
+ * problem or a parametric line without gate_s, and none set); ATO_ERR_ARG: samples outside [1, 64], batch < 1,
+ * unknown layout, axial_tol negative or NaN, more than 64 gates; nothing is launched or written then. */
+#define ATO_GATECHECK_NCH 9
+typedef struct ato_gate_plane {
+    double centre[3];
+    double R[9];          /* row-major, columns e1 e2 e3 */
+    double d_max;
+    int32_t shape;        /* ATO_GATE_CIRCLE / ATO_GATE_SQUARE */
+    int32_t pad;
+} ato_gate_plane;
+/* ato_gatecheck_set_gates synchronises the whole device before it replaces the planes (a queued check may still read
+ * the old ones), as ato_clearance_set_line does: it is a set-up call, not one for a hot path. */
+int ato_gatecheck_set_gates(ato_handle* h, const ato_gate_plane* planes, int32_t n);
+int ato_gatecheck(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t samples, double axial_tol,
+                  double* val, void* stream);
+/* Profiling aid: the same call with only the launches of a bit mask (1 positions, 2 crossings, 4 reduction; 7 is
+ * ato_gatecheck). A launch left out reads what the last whole call left in the handle's buffers, so a subset is
+ * accepted only after a whole call of the same batch, layout, samples and gates on this handle (ATO_ERR_STATE
+ * otherwise). Not part of the check's interface: tools/bench_gatecheck.py is its only user. */
+int ato_gatecheck_launches(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t samples,
+                           double axial_tol, double* val, void* stream, int32_t launches);
 
 /* Per-kernel timing with HIP events recorded on the evaluation stream. ato_timing(h, n)
  * allocates n event slots and starts recording (n = 0 stops); while on, each ato_eval

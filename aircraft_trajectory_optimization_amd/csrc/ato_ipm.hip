@@ -1367,8 +1367,9 @@ int ato_ipm_perturb(int32_t op, int32_t W, int32_t m, const double* prm, int64_t
 
 int ato_ipm_kkt_diag(const ato_ipm_dims* d, const double* Sx, const double* Ss, const double* dw, const double* dc,
                      double* dx, double* dr, double* Ds, void* stream) {
-    if (!d || d->n < 0 || d->mi < 0 || d->meq < 0 || d->mi + d->meq != d->m || d->W <= 0 || !Sx || !dw || !dc ||
-        !dx || !dr || (d->mi && (!Ss || !Ds || !d->iin)) || (d->meq && !d->ieq))
+    // an array of no elements may be null (a problem without constraint rows has no dr), as in the other steps
+    if (!d || d->n < 0 || d->mi < 0 || d->meq < 0 || d->mi + d->meq != d->m || d->W <= 0 || !dw || !dc ||
+        (d->n && (!Sx || !dx)) || (d->m && !dr) || (d->mi && (!Ss || !Ds || !d->iin)) || (d->meq && !d->ieq))
         return fail(ATO_ERR_ARG, "ato_ipm_kkt_diag: arguments");
     const Dev v{d->n, d->m, d->mi, d->meq, d->W, d->iin, d->ieq, nullptr, nullptr, nullptr, nullptr};
     const long long cnt = (long long)(d->n + d->m) * d->W;

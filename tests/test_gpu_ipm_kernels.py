@@ -3,7 +3,10 @@ The fused column kernels of the batched interior-point iteration (include/ato_ip
 solver/ipm_device.py) against the torch formulation of the same steps in solver/batched_ipm.py
 (its CPU path): elementwise results and maxima / minima bit for bit, sums to 1e-13 relative (the
 kernels sum chunk by chunk), on solver states of the racetrack drone problem with random
-iterates; and a whole batched solve with and without the kernels.
+iterates (a few planted on and beyond their bounds), at a width within one 64-column block and at one
+across two, the KKT diagonals (ato_ipm_kkt_diag) included; and a whole batched solve with and without the
+kernels. tests/test_gpu_ipm_columns.py judges the same kernels against a host fp64 oracle on synthetic
+structures that reach every chunk and fold path.
 '''
 import numpy as np
 import pytest
@@ -26,7 +29,9 @@ def _solver(B=5, N=6, K=3, model='drone'):
 
 
 def _state(sol, seed=0):
-    ''' random iterates inside (and a few on / outside) the bounds, multipliers, directions '''
+    ''' random iterates inside the bounds, multipliers, directions; in column 1 and in the last column a few
+    entries are planted on a bound (slack exactly 0) and beyond it (negative slack): the first and the last
+    bounded variable and slack from below, the middle bounded variable from above '''
     g = torch.Generator(device='cuda').manual_seed(seed)
     n, m, B = sol.n, sol.m, sol.B
     mi = len(sol.iin)
@@ -43,6 +48,15 @@ def _state(sol, seed=0):
               zl=rnd(n, B, lo=0.0, hi=2.0), zu=rnd(n, B, lo=0.0, hi=2.0), vl=rnd(mi, B, lo=0.0, hi=2.0),
               vu=rnd(mi, B, lo=0.0, hi=2.0), gf=rnd(n, B), jty=rnd(n, B), dx=rnd(n, B), ds=rnd(mi, B),
               mu=rnd(B, lo=1e-3, hi=0.1), tau=rnd(B, lo=0.9, hi=0.99), f=rnd(B), az=rnd(B, lo=0.0, hi=1.0))
+    for v, L, U in ((st['x'], sol.xL, sol.xU), (st['s'], sol.dL, sol.dU)):
+        for col, off in ((1, 0.0), (B - 1, 0.125)):           # on the bound; beyond it
+            lo = torch.nonzero(torch.isfinite(L[:, col])).reshape(-1).tolist()
+            up = torch.nonzero(torch.isfinite(U[:, col])).reshape(-1).tolist()
+            for e in {lo[0], lo[-1]} if lo else ():
+                v[e, col] = L[e, col] - off
+            if up:
+                e = up[len(up) // 2]
+                v[e, col] = U[e, col] + off
     st['zl'] = torch.where(sol.hxl, st['zl'], 0.0)
     st['zu'] = torch.where(sol.hxu, st['zu'], 0.0)
     st['vl'] = torch.where(sol.hsl, st['vl'], 0.0)
@@ -57,12 +71,19 @@ def _same(a, b):
 
 
 def _close(a, b, rtol=1e-13):
+    ''' sums: equal NaN masks (a column with a planted slack below its bound has log of a negative), equal
+    infinities, the rest to rtol '''
+    nan = torch.isnan(b)
+    assert torch.equal(torch.isnan(a), nan), (a, b)
+    a, b = a[~nan], b[~nan]
     assert torch.allclose(a, b, rtol=rtol, atol=1e-300), ((a - b).abs() / b.abs()).max()
 
 
 @pytest.mark.parametrize('seed', [0, 1])
-def test_errors_rhs_direction_measures_multipliers(seed):
-    sol = _solver()
+@pytest.mark.parametrize('B', [5, 70])
+def test_errors_rhs_direction_measures_multipliers(B, seed):
+    ''' B = 70: the racetrack structure across a 64-column block boundary '''
+    sol = _solver(B)
     vk, o = sol.vk, sol.o
     t = _state(sol, seed)
     bd = sol._bd()
@@ -120,6 +141,20 @@ def test_errors_rhs_direction_measures_multipliers(seed):
     _same(zu, torch.where(sol.hxu, torch.minimum(torch.maximum(rzu, mu / (ks * b)), ks * mu / b), 0.0))
     _same(vl, torch.where(sol.hsl, torch.minimum(torch.maximum(rvl, mu / (ks * c)), ks * mu / c), 0.0))
     _same(vu, torch.where(sol.hsu, torch.minimum(torch.maximum(rvu, mu / (ks * d)), ks * mu / d), 0.0))
+    # ---- KKT diagonals of an inertia-correction pass, against _kkt_diag's torch formulation (vk unset)
+    dw, dc = t['az'] * 1e-4, t['tau'] * 1e-8
+    dw[0] = 0.0
+    dc[B - 1] = 0.0
+    kdx, kdr, kDs = vk.kkt_diag(Sx, Ss, dw, dc)
+    sol.vk = None
+    try:
+        rdx, rdr, rDs = sol._kkt_diag(Sx, Ss, dw, dc)
+    finally:
+        sol.vk = vk
+    _same(kdx, rdx)
+    _same(kdr, rdr)
+    _same(kDs, rDs)
+    assert torch.equal(torch.signbit(kdr.nan_to_num()), torch.signbit(rdr.nan_to_num()))
 
 
 def test_fused_solve_follows_torch_formulation():

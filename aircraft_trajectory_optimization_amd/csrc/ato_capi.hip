@@ -524,6 +524,26 @@ extern "C" int ato_remesh(ato_handle* src, ato_handle* dst, int32_t batch_src, i
     ATO_NOEXCEPT_BODY(remesh_impl(src, dst, batch_src, batch_dst, layout, w_src, cols, w_dst, stream))
 }
 
+static int warmstart_impl(ato_handle* point, ato_handle* drone, int32_t batch, int32_t layout, const double* w_point,
+                          double* w_drone, double* hlb, double* hub, double* info, void* stream) {
+    if (!point || !drone) return fail(ATO_ERR_ARG, "null handle");
+    const ato::ProbD &pp = point->pd, &pd = drone->pd;
+    const char* msg = "";
+    if (int rc = ato::warmstart_check(pp, pd, batch, layout, &msg)) return fail(rc, msg);
+    if (!w_point || !w_drone || !info) return fail(ATO_ERR_ARG, "null buffer");
+    const ato::WarmD a = ato::warmstart_args(pp, pd, point->d_geom, drone->d_geom);
+    const hipError_t e =
+        ato::launch_warmstart(a, pd.att, batch, layout, w_point, w_drone, hlb, hub, info, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("warm-start launch: ") + hipGetErrorString(e));
+    return ATO_OK;
+}
+
+extern "C" int ato_warmstart(ato_handle* point, ato_handle* drone, int32_t batch, int32_t layout,
+                             const double* w_point, double* w_drone, double* hlb, double* hub, double* info,
+                             void* stream) {
+    ATO_NOEXCEPT_BODY(warmstart_impl(point, drone, batch, layout, w_point, w_drone, hlb, hub, info, stream))
+}
+
 static int clearance_set_line_impl(ato_handle* h, const ato_line_table* t) {
     if (!h || !t) return fail(ATO_ERR_ARG, "null argument");
     if (h->L.p.frame == ato::GLOBAL) return ATO_OK;      // not needed: ignored

@@ -9,6 +9,7 @@
 #include "ato_clearance.hpp"
 #include "ato_audit.hpp"
 #include "ato_gatecheck.hpp"
+#include "ato_warmstart.hpp"
 
 // A Lagrange weight table on the device, keyed by a substep or sample count. dev is allocated once (ato_create,
 // sized for the largest key) and holds the table of the key last uploaded; the host tables it is uploaded from

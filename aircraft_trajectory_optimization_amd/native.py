@@ -161,7 +161,7 @@ EXPORTED_SYMBOLS = ('ato_create', 'ato_destroy', 'ato_sizes', 'ato_sparsity', 'a
                     'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity', 'ato_replay_set_lift',
                     'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided', 'ato_clearance_set_line',
                     'ato_clearance', 'ato_audit', 'ato_gatecheck', 'ato_gatecheck_set_gates',
-                    'ato_gatecheck_launches') + IPM_SYMBOLS
+                    'ato_gatecheck_launches', 'ato_warmstart') + IPM_SYMBOLS
 
 
 def library_path() -> str:
@@ -202,6 +202,7 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
         lib.ato_remesh.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp]
         lib.ato_mesh_signed_distance_strided.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int64, vp,
                                                          ctypes.c_int32, vp]
+        lib.ato_warmstart.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp]
         lib.ato_clearance_set_line.argtypes = [vp, ctypes.POINTER(AtoLineTable)]
         lib.ato_clearance.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp,
                                       ctypes.c_int32, vp]
@@ -255,7 +256,7 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
                    'ato_set_instance_spheres', 'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity',
                    'ato_replay_set_lift', 'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided',
                    'ato_clearance_set_line', 'ato_clearance', 'ato_audit', 'ato_gatecheck',
-                   'ato_gatecheck_set_gates', 'ato_gatecheck_launches'):
+                   'ato_gatecheck_set_gates', 'ato_gatecheck_launches', 'ato_warmstart'):
             getattr(lib, fn).restype = ctypes.c_int
     return lib
 
@@ -502,6 +503,23 @@ class NativeProblem:
         NotImplementedError with the library's message.
         '''
         rc = self.remesh_rc(src, batch_src, batch_dst, w_src, w_dst, cols, layout, stream)
+        self._check_supported(rc)
+
+    def warmstart_rc(self, point: 'NativeProblem', batch: int, w_point: int, w_drone: int, info: int, hlb: int = 0,
+                     hub: int = 0, layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0) -> int:
+        ''' ato_warmstart(point -> this drone problem) on device pointers; returns the library's code '''
+        return self.lib.ato_warmstart(point.handle, self.handle, int(batch), int(layout), w_point or None,
+                                      w_drone or None, hlb or None, hub or None, info or None, stream or None)
+
+    def warmstart_ptrs(self, point: 'NativeProblem', batch: int, w_point: int, w_drone: int, info: int, hlb: int = 0,
+                       hub: int = 0, layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0):
+        '''
+        Lift the point-mass decision vectors w_point [point.nw x batch] of the problem `point` into this drone
+        problem's warm starts w_drone [nw x batch] (asynchronous on `stream`; include/ato.h ato_warmstart): info
+        [3 x batch] (status, quat_flip, euler_wraps), hlb / hub [N x batch] or 0. Problems the lift does not cover
+        (RK4 transcription, CPC variables) raise NotImplementedError with the library's message.
+        '''
+        rc = self.warmstart_rc(point, batch, w_point, w_drone, info, hlb, hub, layout, stream)
         self._check_supported(rc)
 
     def clearance_set_line(self, table: dict):

@@ -178,3 +178,49 @@ def drone_guess_batch(drone: ProblemSpec, point: ProblemSpec, XP: np.ndarray):
     wraps = (np.round((last_r - first_r)[:, 0] / 2 / np.pi) if (closed and not veh.use_quat and not dcm)
              else np.zeros(B))
     return W, LBW, UBW, quat_flip, wraps
+
+
+def drone_guess_batch_device(drone: ProblemSpec, point: ProblemSpec, XP, device=None):
+    '''
+    drone_guess_batch on the device (libato's ato_warmstart, csrc/ato_warmstart.hpp): XP is a device tensor
+    [point.nw, B], e.g. the x of the batched point-mass solve as it is, or a host array [B, point.nw]. Returns
+    (W [nw, B], LBW [nw, B], UBW [nw, B], quat_flip [B], euler_wraps [B]): W, LBW and UBW device tensors in the
+    solver's interleaved layout, the other two host arrays. Only the three status values per instance are read
+    back. Raises as drone_guess_batch does: NotImplementedError where the Euler continuity fails (and for RK4 /
+    CPC problems, which the kernels do not cover), and ValueError for an instance with a degenerate node (zero
+    or non-finite thrust or velocity, gimbal-locked Euler angles), where the host version returns NaN.
+    '''
+    import torch
+    from aircraft_trajectory_optimization_amd import native
+    if (drone.N, drone.K) != (point.N, point.K):
+        raise ValueError('warm start needs the same discretisation')
+    if torch.is_tensor(XP) and device is None and XP.is_cuda:
+        device = XP.device
+    device = device or torch.device('cuda', torch.cuda.current_device())
+    if torch.is_tensor(XP):
+        XP = XP.reshape(XP.shape[0], -1).to(device=device, dtype=torch.float64).contiguous()
+    else:
+        XP = torch.as_tensor(np.array(np.atleast_2d(XP), np.float64)).T.contiguous().to(device)
+    if XP.shape[0] != point.nw:
+        raise ValueError(f'point-mass vectors of length {XP.shape[0]}, problem has {point.nw}')
+    B, N = XP.shape[1], drone.N
+    opts = {'device': device, 'dtype': torch.float64}
+    with torch.cuda.device(device):
+        pp, pd = native.NativeProblem(point.native_spec()), native.NativeProblem(drone.native_spec())
+        if drone.nw > N + N * drone.K1 * drone.nv:      # elements the kernels leave unwritten
+            W = torch.as_tensor(drone.w0, **opts)[:, None].repeat(1, B)
+        else:
+            W = torch.empty((drone.nw, B), **opts)
+        LBW = torch.as_tensor(drone.lbw, **opts)[:, None].repeat(1, B)
+        UBW = torch.as_tensor(drone.ubw, **opts)[:, None].repeat(1, B)
+        info = torch.empty((3, B), **opts)
+        # the h rows are the first N of [nw, B]: the kernel writes them in place
+        pd.warmstart_ptrs(pp, B, XP.data_ptr(), W.data_ptr(), info.data_ptr(), LBW.data_ptr(), UBW.data_ptr(),
+                          stream=torch.cuda.current_stream(device).cuda_stream)
+        status, flips, wraps = info.cpu().numpy()
+    if np.any(status == 1):
+        raise NotImplementedError('Warmstart continuity failed for euler angles, try quaternion')
+    if np.any(status == 2):
+        raise ValueError(f'warm start: instance {int(np.argmax(status == 2))} has a degenerate node (zero or '
+                         'non-finite thrust or velocity, or gimbal-locked Euler angles)')
+    return W, LBW, UBW, flips > 0, wraps

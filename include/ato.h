@@ -252,6 +252,39 @@ int ato_replay(ato_handle* h, int32_t batch, int32_t layout, const double* w, in
 int ato_remesh(ato_handle* src, ato_handle* dst, int32_t batch_src, int32_t batch_dst, int32_t layout,
                const double* w_src, const int32_t* cols, double* w_dst, void* stream);
 
+/* Lift of point-mass racelines into drone warm starts (csrc/ato_warmstart.hpp; raceline/warmstart.py drone_guess,
+ * the reference's use_ws path, drone_raceline.py:158-274). point is a point-mass problem, drone a drone problem of
+ * any pose and frame over the same N and K, both collocation transcriptions. Per instance and node (n, k), from the
+ * point-mass node's state, thrust and thrust rate, rotated to the global frame by the point problem's own R_p when
+ * its attitude is the relative one:
+ *   position   the point-mass node's
+ *   attitude   R = [e1 e2 e3], e3 = T / |T|, e1 = v / |v| made orthogonal to e3, e2 = e3 x e1 (closed lines), the
+ *              rotation of e_z onto T / |T| (open lines); left-multiplied by the drone problem's R_p^T when its
+ *              attitude is the relative one; stored as R row-major (DCM), as the quaternion (qi, qj, qk, qr) with
+ *              its sign continuous along the lap (a node at distance >= 1 of its predecessor is negated), or as
+ *              (yaw, pitch, roll) = (atan2(R10, R00), -asin(R20), atan2(R21, R22)) with the yaw unwrapped by one
+ *              turn where two nodes are more than 1 apart
+ *   body velocity R^T v, body rates R^T (T x dT) / |T|^2, rotor thrusts |T| / 4, thrust rates 0
+ *   h_n        the point-mass step size; hlb, hub [N x batch] (either may be NULL) receive h_n / 100 and 10 h_n
+ * Elements of w_drone that are neither a step size nor a node variable are left unwritten: pre-fill them. Nothing is
+ * clipped or renormalised. info [3 x batch] (doubles, in `layout`):
+ *   0  status       0 ok; 1 the Euler unwrap failed (two nodes stay more than 1 apart: use the quaternion pose);
+ *                   2 a node is degenerate: |T|, |v|, the orthogonalised |e1| (closed) or |T x e_z| / |T| (open) is
+ *                   zero or not finite, or an Euler node has |R20| >= 1 - 1e-12 (gimbal lock). What the arithmetic
+ *                   gives is written all the same, NaN included.
+ *   1  quat_flip    1 when first and last quaternion of the lap are more than 1 apart (closed lines; the closure row
+ *                   then is q_F + q_0, ato_problem_desc.quat_flip), else 0
+ *   2  euler_wraps  whole turns of the yaw between first and last node (closed lines, Euler pose), else 0
+ * w_point [nw_p x batch], w_drone [nw_d x batch], both in `layout`. Two launches on the stream for the DCM pose
+ * (info cleared, nodes), three for the others (the continuity chain, cut into segments per instance); asynchronous,
+ * no allocation, no device-wide synchronisation, no host read-back, no atomics. Not covered: RK4 transcriptions, the
+ * CPC progress variables of a drone problem, obstacle-tube tables.
+ * ATO_ERR_ARG: batch < 1, unknown layout, point not a point mass, drone not a drone, different N or K, NULL w_point,
+ * w_drone or info; ATO_ERR_UNSUPPORTED: an RK4-transcribed problem on either side, a drone problem that carries CPC
+ * progress variables; nothing is launched or written then. */
+int ato_warmstart(ato_handle* point, ato_handle* drone, int32_t batch, int32_t layout, const double* w_point,
+                  double* w_drone, double* hlb, double* hub, double* info, void* stream);
+
 /* Clearance of collocation solutions from an obstacle mesh (csrc/ato_clearance.hpp): per (instance, interval,
  * sample) the global position of the interval's own polynomial, sum_j l_j(x_i) Z[n, j, 0..2], and its signed
  * distance to the mesh. samples = S in [1, 64]: S + 1 points per interval at x_i = i / S, both ends; samples = 0:

@@ -60,6 +60,8 @@ static void release(ato_handle* h) {
     (void)hipFree(h->d_clear_pos);
     (void)hipFree(h->d_gate_tau);       // the planes follow tau in the same allocation
     (void)hipFree(h->d_gate_part);
+    (void)hipFree(h->d_export_D);
+    (void)hipFree(h->d_export_ts);
     for (ato_weight_cache* c : {&h->replay_w, &h->clear_w, &h->audit_w}) (void)hipFree(c->dev);
     h->remesh_tabs.clear();
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
@@ -169,6 +171,13 @@ static int create_impl(const ato_problem_desc* desc, ato_handle** out) {
             delete h;
             return fail(ATO_ERR_HIP, "gate planes: upload failed");
         }
+    }
+    // export: the end weights D_0 .. D_K (tau is the gate passage's copy)
+    if (hipMalloc((void**)&h->d_export_D, (ATO_KMAX + 1) * sizeof(double)) != hipSuccess ||
+        hipMemcpy(h->d_export_D, h->L.p.D, (ATO_KMAX + 1) * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        release(h);
+        delete h;
+        return fail(ATO_ERR_HIP, "export end weights: allocation or upload failed");
     }
     h->pd = h->L.p;
     h->pd.geom = h->d_geom;
@@ -710,6 +719,32 @@ extern "C" int ato_gatecheck(ato_handle* h, int32_t batch, int32_t layout, const
 extern "C" int ato_gatecheck_launches(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t samples,
                                       double axial_tol, double* val, void* stream, int32_t launches) {
     ATO_NOEXCEPT_BODY(gatecheck_impl(h, batch, layout, w, samples, axial_tol, val, stream, launches))
+}
+
+static int export_impl(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t n_times,
+                       const double* times, int32_t relative, double* nodes, double* state, void* stream) {
+    if (!h) return fail(ATO_ERR_ARG, "null handle");
+    const ato::ProbD& p = h->pd;
+    const char* msg = "";
+    if (int rc = ato::export_check(p, h->d_line != nullptr, batch, layout, n_times, w != nullptr, times != nullptr,
+                                   nodes != nullptr, state != nullptr, &msg))
+        return fail(rc, msg);
+    if (int rc = grow(&h->d_export_ts, &h->export_ts_len, (size_t)(p.N + 1) * batch,
+                      "export start times: out of device memory"))
+        return rc;
+    const ato::ExportD a =
+        ato::export_args(p, n_times, relative, h->d_gate_tau, h->d_export_D, times, h->d_export_ts, h->line);
+    hipError_t e = hipErrorInvalidValue;
+    ato::with_model(p, [&]<class M>() {
+        e = ato::launch_export<M>(a, batch, layout, w, nodes, state, (hipStream_t)stream);
+    });
+    if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("export launch: ") + hipGetErrorString(e));
+    return ATO_OK;
+}
+
+extern "C" int ato_export(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t n_times,
+                          const double* times, int32_t relative, double* nodes, double* state, void* stream) {
+    ATO_NOEXCEPT_BODY(export_impl(h, batch, layout, w, n_times, times, relative, nodes, state, stream))
 }
 
 extern "C" int ato_eval(ato_handle* h, int32_t batch, int32_t layout, const double* w, double* g,

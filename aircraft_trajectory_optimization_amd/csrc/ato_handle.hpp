@@ -10,6 +10,7 @@
 #include "ato_audit.hpp"
 #include "ato_gatecheck.hpp"
 #include "ato_warmstart.hpp"
+#include "ato_export.hpp"
 
 // A Lagrange weight table on the device, keyed by a substep or sample count. dev is allocated once (ato_create,
 // sized for the largest key) and holds the table of the key last uploaded; the host tables it is uploaded from
@@ -107,4 +108,9 @@ struct ato_handle {
     double* d_gate_part = nullptr;
     size_t gate_part_len = 0;
     int64_t gate_last[4] = {-1, -1, -1, -1};   // batch, layout, samples, G of the last whole call (ato_gatecheck_launches)
+    // export (ato_export.hpp): D_0 .. D_K (ato_create; tau is d_gate_tau) and the interval start times
+    // [N + 1][B] (grown only when a call needs more)
+    double* d_export_D = nullptr;
+    double* d_export_ts = nullptr;
+    size_t export_ts_len = 0;
 };

@@ -76,33 +76,7 @@ inline WarmD warmstart_args(const ProbD& pt, const ProbD& dr, const double* geom
 
 ATO_HD bool ws_bad(double x) { return !(x > 0.0 && x <= 1.79769313486231570815e308); }
 
-// Unit quaternion (qi, qj, qk, qr) of a rotation matrix, restated from the algorithm SciPy documents for
-// Rotation.from_matrix / as_quat (Markley 2008, "Unit quaternion from rotation matrix"): of m00, m11, m22 and the
-// trace the largest decides (the first of equals); for a diagonal entry i, with j, k the next two axes cyclically,
-//   q_i = 1 - trace + 2 m_ii, q_j = m_ji + m_ij, q_k = m_ki + m_ik, q_r = m_kj - m_jk
-// and for the trace
-//   q_i = m_21 - m_12, q_j = m_02 - m_20, q_k = m_10 - m_01, q_r = 1 + trace;
-// the four are divided by their norm. No canonical sign is applied. (The installed SciPy is the tests' oracle.)
-ATO_HD void ws_quat(const double* R, double* q) {
-    const double tr = R[0] + R[4] + R[8];
-    int c = 0;
-    double best = R[0];
-    if (R[4] > best) { best = R[4]; c = 1; }
-    if (R[8] > best) { best = R[8]; c = 2; }
-    if (tr > best) c = 3;
-    if (c == 0) {
-        q[0] = 1.0 - tr + 2.0 * R[0]; q[1] = R[3] + R[1]; q[2] = R[6] + R[2]; q[3] = R[7] - R[5];
-    } else if (c == 1) {
-        q[1] = 1.0 - tr + 2.0 * R[4]; q[2] = R[7] + R[5]; q[0] = R[1] + R[3]; q[3] = R[2] - R[6];
-    } else if (c == 2) {
-        q[2] = 1.0 - tr + 2.0 * R[8]; q[0] = R[2] + R[6]; q[1] = R[5] + R[7]; q[3] = R[3] - R[1];
-    } else {
-        q[0] = R[7] - R[5]; q[1] = R[2] - R[6]; q[2] = R[3] - R[1]; q[3] = 1.0 + tr;
-    }
-    const double nq = sqrt(fma(q[3], q[3], fma(q[2], q[2], fma(q[1], q[1], q[0] * q[0]))));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) q[i] = q[i] / nq;
-}
+// ws_quat(): rotation matrix -> unit quaternion, in the sampling layer (ato_sample.hpp; the export shares it)
 
 // Pass 1: node p of one instance. wp / wd point at the instance's element 0 of the point-mass and the drone
 // decision vector, element strides sp / sd. Returns whether the node is degenerate (status 2).

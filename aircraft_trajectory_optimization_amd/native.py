@@ -22,6 +22,7 @@ ATO_LAYOUT_INTERLEAVED, ATO_LAYOUT_INSTANCE_MAJOR = 0, 1
 ATO_AUDIT_NCH = 14      # channels per item of ato_audit
 ATO_GATECHECK_NCH = 9   # channels per (gate, instance) of ato_gatecheck
 GATE_MAX = 64           # gates per ato_gatecheck call
+ATO_EXPORT_NCH = 30     # channels per (time, instance) of ato_export's state table
 ATO_OK, ATO_ERR_ARG, ATO_ERR_UNSUPPORTED, ATO_ERR_HIP, ATO_ERR_STATE = 0, -1, -2, -3, -4
 ABI_VERSION = 3
 CPC_MAX = 16                 # ATO_CPC_MAX
@@ -161,7 +162,7 @@ EXPORTED_SYMBOLS = ('ato_create', 'ato_destroy', 'ato_sizes', 'ato_sparsity', 'a
                     'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity', 'ato_replay_set_lift',
                     'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided', 'ato_clearance_set_line',
                     'ato_clearance', 'ato_audit', 'ato_gatecheck', 'ato_gatecheck_set_gates',
-                    'ato_gatecheck_launches', 'ato_warmstart') + IPM_SYMBOLS
+                    'ato_gatecheck_launches', 'ato_warmstart', 'ato_export') + IPM_SYMBOLS
 
 
 def library_path() -> str:
@@ -203,6 +204,7 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
         lib.ato_mesh_signed_distance_strided.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int64, vp,
                                                          ctypes.c_int32, vp]
         lib.ato_warmstart.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp]
+        lib.ato_export.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, vp]
         lib.ato_clearance_set_line.argtypes = [vp, ctypes.POINTER(AtoLineTable)]
         lib.ato_clearance.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp,
                                       ctypes.c_int32, vp]
@@ -256,7 +258,7 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
                    'ato_set_instance_spheres', 'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity',
                    'ato_replay_set_lift', 'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided',
                    'ato_clearance_set_line', 'ato_clearance', 'ato_audit', 'ato_gatecheck',
-                   'ato_gatecheck_set_gates', 'ato_gatecheck_launches', 'ato_warmstart'):
+                   'ato_gatecheck_set_gates', 'ato_gatecheck_launches', 'ato_warmstart', 'ato_export'):
             getattr(lib, fn).restype = ctypes.c_int
     return lib
 
@@ -591,6 +593,23 @@ class NativeProblem:
         RK4-transcribed problems raise NotImplementedError with the library's message.
         '''
         rc = self.gatecheck_rc(batch, w, samples, val, axial_tol, layout, stream)
+        self._check_supported(rc)
+
+    def export_rc(self, batch: int, w: int, n_times: int, times: int, relative: bool = False, nodes: int = 0,
+                  state: int = 0, layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0) -> int:
+        ''' ato_export on device pointers; returns the library's code (ato_last_error has the message) '''
+        return self.lib.ato_export(self.handle, int(batch), int(layout), w or None, int(n_times), times or None,
+                                   int(bool(relative)), nodes or None, state or None, stream or None)
+
+    def export_ptrs(self, batch: int, w: int, n_times: int, times: int, relative: bool = False, nodes: int = 0,
+                    state: int = 0, layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0):
+        '''
+        The decision vectors w over the device time array times [n_times] (asynchronous on `stream`; include/ato.h
+        ato_export): seconds, or fractions of every instance's own lap time with `relative`. nodes [NV x n_times
+        batch] (the interpolated node vectors) and state [ATO_EXPORT_NCH x n_times batch] (the global-frame table)
+        in `layout`; either may be 0. RK4-transcribed problems raise NotImplementedError with the library's message.
+        '''
+        rc = self.export_rc(batch, w, n_times, times, relative, nodes, state, layout, stream)
         self._check_supported(rc)
 
     def timing_start(self, max_calls: int):

@@ -288,6 +288,38 @@ class BatchedNLP:
                                     layout=self.layout, stream=st.cuda_stream)
         return val
 
+    def export(self, W=None, times=None, relative: bool = False, nodes: bool = False, stream=None):
+        '''
+        Decision vectors as global-frame state tables over a list of times shared by all instances (ato_export,
+        asynchronous on `stream`). times: host sequence or device tensor (n_times,), seconds, or with `relative`
+        fractions of every instance's own lap time. W as in audit(). Returns (state, nodes) in the layout:
+        interleaved (NCH, n_times, B), (NV, n_times, B); instance-major (B, n_times, NCH), (B, n_times, NV); nodes
+        (the reference's z_interp, u_interp, du_interp in the problem's own frame) is None unless asked for. The
+        state channels (t, interval, x, position, quaternion, velocities, rates, inputs, input rates, (s, y, n))
+        are listed in include/ato.h; before the start and after the end of the lap the values are held. One stream
+        per problem handle: the start times are handle state. RK4-transcribed problems raise NotImplementedError.
+        '''
+        B = self.batch
+        il = self.layout == native.ATO_LAYOUT_INTERLEAVED
+        W = self._columns(W, 'export')
+        if times is None:
+            raise ValueError('export needs times')
+        opts = {'device': self.device, 'dtype': torch.float64}
+        times = (times if torch.is_tensor(times) else torch.as_tensor(np.array(times, np.float64))).to(**opts)
+        times = times.reshape(-1).contiguous()
+        T = int(times.numel())
+        self._ensure_line()
+        nch, nv = native.ATO_EXPORT_NCH, self.spec.nv
+        state = torch.empty((nch, T, B) if il else (B, T, nch), **opts)
+        nod = torch.empty((nv, T, B) if il else (B, T, nv), **opts) if nodes else None
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if stream is not None:      # temporaries made on the current stream, read on another
+            W.record_stream(st)
+            times.record_stream(st)
+        self.problem.export_ptrs(B, W.data_ptr(), T, times.data_ptr(), relative, nod.data_ptr() if nodes else 0,
+                                 state.data_ptr(), layout=self.layout, stream=st.cuda_stream)
+        return state, nod
+
     def remesh_from(self, src: 'BatchedNLP', W_src, cols=None, stream=None) -> torch.Tensor:
         '''
         Transfer decision vectors of the batch `src` (the same scenario on a coarser mesh: this N a multiple

@@ -158,6 +158,17 @@ class _Raceline:
         from aircraft_trajectory_optimization_amd.raceline.gates import gate_passage
         return gate_passage(self.spec, self._solution_vector(results)[None], samples=samples, tol=tol)
 
+    def export(self, results=None, times=None, count: Optional[int] = None, rate: Optional[float] = None):
+        '''
+        A solution of this problem as a global-frame state table over time, on the device (raceline/export.py):
+        position, body -> global quaternion, global and body velocity, body rates, inputs and input rates at
+        `times` (seconds), at `count` equal lap fractions, or every 1 / `rate` seconds. `results` is a
+        RacelineResults of solve() (default: the last one) or a decision vector. Returns the ExportResult of that
+        one instance. It reports the solution, it certifies nothing. RK4 transcriptions raise NotImplementedError.
+        '''
+        from aircraft_trajectory_optimization_amd.raceline.export import export_solutions
+        return export_solutions(self.spec, self._solution_vector(results)[None], times=times, count=count, rate=rate)
+
     def _solution_vector(self, results_or_x=None) -> np.ndarray:
         ''' the decision vector of a RacelineResults of solve() (default: the last one), or the vector itself '''
         if results_or_x is None or isinstance(results_or_x, RacelineResults):

@@ -396,6 +396,43 @@ int ato_gatecheck(ato_handle* h, int32_t batch, int32_t layout, const double* w,
 int ato_gatecheck_launches(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t samples,
                            double axial_tol, double* val, void* stream, int32_t launches);
 
+/* Export of collocation solutions as state tables on a time grid (csrc/ato_export.hpp): per (time j, instance b)
+ * the reference's z_interp, u_interp, du_interp (utils/discretization_utils.interpolate_collocation) and a lift to
+ * the global frame. times: device array [n_times] shared by all instances, seconds, or with relative != 0
+ * fractions of each instance's own lap time T_b (t = times[j] * T_b). Interval start times are the sequential fp64
+ * sum t_start[n + 1] = t_start[n] + h_n (numpy.cumsum bit for bit), T_b = t_start[N]; the interval of t is
+ * n = (number of t_start[0..N] <= t) - 1. t < 0 holds the first node X[0, 0] (n = -1, x = 0); t >= T_b holds the
+ * end value sum_k D_k X[N - 1, k] (n = N, x = 1); else x = (t - t_start[n]) / h_n and every component is
+ * sum_k l_k(x) X[n, k], k ascending, l_k the product formula. A NaN time gives NaN in every channel. A closed line
+ * does not wrap t beyond the lap: values are held, as in the reference.
+ * nodes (or NULL): the NV components (z, u, du) in the problem's own frame and parameterisation. state (or NULL):
+ * ATO_EXPORT_NCH channels, NaN where the problem has none:
+ *   0      t used (seconds)       1  interval n (-1, 0 .. N - 1, N)       2  abscissa x
+ *   3-5    global position (parametric: x_c(s) + y e_y(s) + n e_n(s) at the sample's own s; needs the table of
+ *          ato_clearance_set_line)
+ *   6-9    body -> global quaternion (qi, qj, qk, qr): for the ESP pose with a global attitude r as interpolated,
+ *          unnormalised; else the unit quaternion (the algorithm of ato_warmstart) of the rotation nearest to R,
+ *          U V^T of its SVD, as SciPy's Rotation.from_matrix treats a matrix that is not orthonormal (det R <= 0
+ *          or a NaN / inf entry: NaN, where SciPy raises). Along the samples, in the order of `times`, q_j is negated when its dot product with the
+ *          already-signed q_{j-1} is negative.
+ *   10-12  global velocity R vb; R = R(r), for the relative attitude [e_s e_y e_n](s) R(r); nothing is
+ *          renormalised. Point mass: its own velocity components
+ *   13-15  body velocity, 16-18 body rates (drone)
+ *   19-22  inputs (4 rotor thrusts; point mass: 3 thrust components), 23-26 input rates
+ *   27-29  (s, y, n) (parametric)
+ * Channel c of item (j, b) of an output with C channels is at [(c n_times + j) batch + b] (interleaved) or
+ * [(b n_times + j) C + c] (instance-major); w [nw x batch] in `layout`. Two launches on the stream (start times,
+ * samples) and a third for the sign of a drone's state table; asynchronous, no device-wide synchronisation, no
+ * atomics. The start times live in a buffer on the handle, grown only when a call needs more: ONE stream per
+ * handle. Not covered: RK4 transcriptions, per-instance time arrays, fp32, CPC progress variables (not read), the
+ * trajectory as flown (ato_replay's traj). It certifies nothing: replay, audit, clearance and gate check judge.
+ * ATO_ERR_UNSUPPORTED: RK4 transcription; ATO_ERR_STATE: a parametric problem without its centreline table;
+ * ATO_ERR_ARG: batch < 1, n_times < 1, unknown layout, NULL w or times, nodes and state both NULL; nothing is
+ * launched or written then. */
+#define ATO_EXPORT_NCH 30
+int ato_export(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t n_times, const double* times,
+               int32_t relative, double* nodes, double* state, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the evaluation stream. ato_timing(h, n)
  * allocates n event slots and starts recording (n = 0 stops); while on, each ato_eval
  * records events around its Jacobian kernel and its cost-reduction kernel. ato_timing_read

@@ -62,6 +62,8 @@ static void release(ato_handle* h) {
     (void)hipFree(h->d_gate_part);
     (void)hipFree(h->d_export_D);
     (void)hipFree(h->d_export_ts);
+    (void)hipFree(h->d_ext_tab);
+    (void)hipFree(h->d_ext_part);
     for (ato_weight_cache* c : {&h->replay_w, &h->clear_w, &h->audit_w}) (void)hipFree(c->dev);
     h->remesh_tabs.clear();
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
@@ -178,6 +180,18 @@ static int create_impl(const ato_problem_desc* desc, ato_handle** out) {
         release(h);
         delete h;
         return fail(ATO_ERR_HIP, "export end weights: allocation or upload failed");
+    }
+    // extrema: the Lagrange -> Bernstein table and tau behind it (collocation only: RK4 has no polynomial)
+    if (h->L.p.trans == ATO_TRANS_COLLOCATION) {
+        const int K1 = h->L.p.K1;
+        std::vector<double> tab((size_t)K1 * K1 + K1);
+        ato::extrema_table(h->L.p.tau, K1, tab.data());
+        std::copy(h->L.p.tau, h->L.p.tau + K1, tab.begin() + (size_t)K1 * K1);
+        if (upload(tab, &h->d_ext_tab) != ATO_OK) {
+            release(h);
+            delete h;
+            return fail(ATO_ERR_HIP, "extrema table: allocation or upload failed");
+        }
     }
     h->pd = h->L.p;
     h->pd.geom = h->d_geom;
@@ -745,6 +759,35 @@ static int export_impl(ato_handle* h, int32_t batch, int32_t layout, const doubl
 extern "C" int ato_export(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t n_times,
                           const double* times, int32_t relative, double* nodes, double* state, void* stream) {
     ATO_NOEXCEPT_BODY(export_impl(h, batch, layout, w, n_times, times, relative, nodes, state, stream))
+}
+
+static int extrema_impl(ato_handle* h, int32_t batch, int32_t layout, const double* w, double* val, double* ival,
+                        void* stream) {
+    if (!h) return fail(ATO_ERR_ARG, "null handle");
+    const ato::ProbD& p = h->pd;
+    const char* msg = "";
+    if (int rc = ato::extrema_check(p, batch, layout, w != nullptr, val != nullptr, &msg)) return fail(rc, msg);
+    if (p.K1 < 2 || p.K1 > ATO_KMAX + 1 || !h->d_ext_tab) return fail(ATO_ERR_STATE, "extrema: no conversion table");
+    const int NVX = ato::extrema_nvx(p), nsplit = ato::extrema_nsplit(p.N, NVX, batch);
+    if (nsplit > 1)
+        if (int rc = grow(&h->d_ext_part, &h->ext_part_len, (size_t)nsplit * ato::EXT_NCH * NVX * batch,
+                          "extrema records: out of device memory"))
+            return rc;
+    const ato::ExtD a = ato::extrema_args(p, nsplit, h->d_ext_tab);
+    const hipError_t e = ato::launch_extrema(a, batch, layout, w, h->d_ext_part, val, ival, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("extrema launch: ") + hipGetErrorString(e));
+    return ATO_OK;
+}
+
+extern "C" int ato_extrema(ato_handle* h, int32_t batch, int32_t layout, const double* w, double* val, double* ival,
+                           void* stream) {
+    ATO_NOEXCEPT_BODY(extrema_impl(h, batch, layout, w, val, ival, stream))
+}
+
+extern "C" int ato_extrema_table(const double* tau, int32_t K1, double* T) {
+    if (!tau || !T || K1 < 2 || K1 > ATO_KMAX + 1) return fail(ATO_ERR_ARG, "extrema table: K1 must be in [2, 10]");
+    ato::extrema_table(tau, K1, T);
+    return ATO_OK;
 }
 
 extern "C" int ato_eval(ato_handle* h, int32_t batch, int32_t layout, const double* w, double* g,

@@ -11,6 +11,7 @@
 #include "ato_gatecheck.hpp"
 #include "ato_warmstart.hpp"
 #include "ato_export.hpp"
+#include "ato_extrema.hpp"
 
 // A Lagrange weight table on the device, keyed by a substep or sample count. dev is allocated once (ato_create,
 // sized for the largest key) and holds the table of the key last uploaded; the host tables it is uploaded from
@@ -113,4 +114,9 @@ struct ato_handle {
     double* d_export_D = nullptr;
     double* d_export_ts = nullptr;
     size_t export_ts_len = 0;
+    // extrema (ato_extrema.hpp): the Lagrange -> Bernstein table [K1][K1] followed by tau [K1] (ato_create) and the
+    // partial records [nsplit][NCH][NVX][B] of calls that split the lap (grown only when a call needs more)
+    double* d_ext_tab = nullptr;
+    double* d_ext_part = nullptr;
+    size_t ext_part_len = 0;
 };

@@ -23,6 +23,7 @@ ATO_AUDIT_NCH = 14      # channels per item of ato_audit
 ATO_GATECHECK_NCH = 9   # channels per (gate, instance) of ato_gatecheck
 GATE_MAX = 64           # gates per ato_gatecheck call
 ATO_EXPORT_NCH = 30     # channels per (time, instance) of ato_export's state table
+ATO_EXTREMA_NCH = 8     # channels per (variable, instance) of ato_extrema
 ATO_OK, ATO_ERR_ARG, ATO_ERR_UNSUPPORTED, ATO_ERR_HIP, ATO_ERR_STATE = 0, -1, -2, -3, -4
 ABI_VERSION = 3
 CPC_MAX = 16                 # ATO_CPC_MAX
@@ -162,7 +163,8 @@ EXPORTED_SYMBOLS = ('ato_create', 'ato_destroy', 'ato_sizes', 'ato_sparsity', 'a
                     'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity', 'ato_replay_set_lift',
                     'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided', 'ato_clearance_set_line',
                     'ato_clearance', 'ato_audit', 'ato_gatecheck', 'ato_gatecheck_set_gates',
-                    'ato_gatecheck_launches', 'ato_warmstart', 'ato_export') + IPM_SYMBOLS
+                    'ato_gatecheck_launches', 'ato_warmstart', 'ato_export', 'ato_extrema',
+                    'ato_extrema_table') + IPM_SYMBOLS
 
 
 def library_path() -> str:
@@ -205,6 +207,8 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
                                                          ctypes.c_int32, vp]
         lib.ato_warmstart.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp]
         lib.ato_export.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, vp]
+        lib.ato_extrema.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp]
+        lib.ato_extrema_table.argtypes = [_c_double_p, ctypes.c_int32, _c_double_p]
         lib.ato_clearance_set_line.argtypes = [vp, ctypes.POINTER(AtoLineTable)]
         lib.ato_clearance.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp,
                                       ctypes.c_int32, vp]
@@ -258,7 +262,8 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
                    'ato_set_instance_spheres', 'ato_sphere_rows', 'ato_gradf_mode', 'ato_gradf_sparsity',
                    'ato_replay_set_lift', 'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided',
                    'ato_clearance_set_line', 'ato_clearance', 'ato_audit', 'ato_gatecheck',
-                   'ato_gatecheck_set_gates', 'ato_gatecheck_launches', 'ato_warmstart', 'ato_export'):
+                   'ato_gatecheck_set_gates', 'ato_gatecheck_launches', 'ato_warmstart', 'ato_export', 'ato_extrema',
+                   'ato_extrema_table'):
             getattr(lib, fn).restype = ctypes.c_int
     return lib
 
@@ -612,6 +617,24 @@ class NativeProblem:
         rc = self.export_rc(batch, w, n_times, times, relative, nodes, state, layout, stream)
         self._check_supported(rc)
 
+    def extrema_rc(self, batch: int, w: int, val: int, ival: int = 0, layout: int = ATO_LAYOUT_INTERLEAVED,
+                   stream: int = 0) -> int:
+        ''' ato_extrema on device pointers; returns the library's code (ato_last_error has the message) '''
+        return self.lib.ato_extrema(self.handle, int(batch), int(layout), w or None, val or None, ival or None,
+                                    stream or None)
+
+    def extrema_ptrs(self, batch: int, w: int, val: int, ival: int = 0, layout: int = ATO_LAYOUT_INTERLEAVED,
+                     stream: int = 0):
+        '''
+        Extrema of every node-vector component of the decision vectors w over whole intervals (asynchronous on
+        `stream`; include/ato.h ato_extrema): val [ATO_EXTREMA_NCH x NVX x batch] (interleaved) or [batch x NVX x
+        ATO_EXTREMA_NCH], NVX = NV + 1 for parametric problems (the last channel is s'); ival (or 0): the
+        per-interval min and max, [NVX x N x 2 x batch] or [batch x NVX x N x 2]. RK4-transcribed problems raise
+        NotImplementedError with the library's message.
+        '''
+        rc = self.extrema_rc(batch, w, val, ival, layout, stream)
+        self._check_supported(rc)
+
     def timing_start(self, max_calls: int):
         ''' record HIP events around the kernels of the next max_calls evaluations '''
         self._check(self.lib.ato_timing(self.handle, int(max_calls)))
@@ -637,3 +660,13 @@ class NativeProblem:
             self.close()
         except Exception:  # pylint: disable=broad-except
             pass
+
+
+def extrema_table(tau) -> 'np.ndarray':
+    ''' the Lagrange -> Bernstein table [K1, K1] ato_extrema applies for the abscissae tau (host only) '''
+    tau = np.ascontiguousarray(tau, np.float64)
+    T = np.empty((len(tau), len(tau)), np.float64)
+    lib = load()
+    if lib.ato_extrema_table(tau.ctypes.data_as(_c_double_p), len(tau), T.ctypes.data_as(_c_double_p)) != ATO_OK:
+        raise ValueError(lib.ato_last_error().decode())
+    return T

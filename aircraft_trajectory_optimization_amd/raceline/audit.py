@@ -121,3 +121,75 @@ def audit_solutions(spec: ProblemSpec, X, samples: int = 16, LBW=None, UBW=None,
     with torch.cuda.device(nlp.device):
         val = nlp.audit(X, samples=int(samples), lb=lb, ub=ub)
         return reduce_audit(val, int(samples), tol, varying)
+
+
+EXTREMA_GROUPS = MARGINS[:7]      # the polynomial channels of the audit: pos, att, vel, rate, u, du, sdot
+
+
+@dataclass
+class ExtremaResult:
+    ''' device tensors of the whole-interval extrema of B instances; NVX = NV (+ 1: s', parametric) channels '''
+    val: torch.Tensor            # (NCH, NVX, B) min, its n and x, max, its n and x, slack, flag (include/ato.h)
+    var_margin: torch.Tensor     # (NV, B) min(min - lb, ub - max) per component of the node vector
+    margin: torch.Tensor         # (B, 7) the audit's channels 0-6 over whole intervals; +inf where a group is empty
+    overshoot: torch.Tensor      # (NV, B) max(0, -var_margin): how far a bound would have to be tightened
+    passed: torch.Tensor         # (B,) every group margin >= -tol (a NaN margin fails)
+    certified: torch.Tensor      # (B,) every (margin - slack) >= -tol and every flag == 0
+    tol: float = 1e-6
+
+
+def extrema_groups(spec: ProblemSpec):
+    ''' the node-vector components of the audit's groups 0-5, as ato_audit sorts them '''
+    iv = spec.nz - 6 if spec.is_drone else 3
+    edges = (0, 3, iv, iv + 3, spec.nz, spec.nz + spec.nu, spec.nv)
+    return [range(edges[g], edges[g + 1]) for g in range(6)]
+
+
+def extrema_solutions(spec: ProblemSpec, X, tol: float = 1e-6, lb=None, ub=None,
+                      device: Optional[torch.device] = None) -> ExtremaResult:
+    '''
+    Hold decision vectors X of the problem `spec` (as audit_solutions takes them) to their variable bounds and to
+    s' >= 0 over WHOLE intervals: libato's ato_extrema encloses the minimum and maximum of every component's
+    collocation polynomial, so `certified` closes the arc between samples for the audit's channels 0-6 (and only
+    for those: the ODE defects, the regularity and the thrust ball are not polynomial and stay the audit's).
+    lb, ub: bounds per component of the node vector, (NV,) shared or (B, NV) per instance (default:
+    path_bounds(spec), which raises where a bound differs between nodes).
+    '''
+    if torch.is_tensor(X):
+        X = X.reshape(X.shape[0], -1).to(torch.float64)
+        B = X.shape[1]
+    else:
+        X = np.atleast_2d(np.asarray(X, np.float64))
+        B = X.shape[0]
+    if (lb is None) != (ub is None):
+        raise ValueError('lb and ub must both be given or both be None')
+    if lb is None:
+        lb, ub = path_bounds(spec)
+    # host arrays or tensors of any device, as BatchedNLP.audit takes them
+    lb, ub = (v.to(torch.float64) if torch.is_tensor(v) else torch.as_tensor(np.array(v, np.float64)) for v in (lb, ub))
+    if lb.shape != ub.shape or tuple(lb.shape) not in ((spec.nv,), (B, spec.nv)):
+        raise ValueError(f'lb and ub must both be ({spec.nv},) or ({B}, {spec.nv})')
+    nlp = BatchedNLP(spec, B, layout=native.ATO_LAYOUT_INTERLEAVED, device=device, buffers=False)
+    if torch.is_tensor(X):
+        X = X.to(nlp.device)
+    with torch.cuda.device(nlp.device):
+        val, _ = nlp.extrema(X)
+        lb, ub = (v.to(nlp.device) for v in (lb, ub))
+        lb, ub = (v.T if v.dim() == 2 else v[:, None] for v in (lb, ub))      # (NV, B) or (NV, 1)
+        nv = spec.nv
+        mn, mx, slack, flag = val[0], val[3], val[6], val[7]
+        var_margin = torch.minimum(mn[:nv] - lb, ub - mx[:nv])
+        inf = torch.full((1, B), float('inf'), device=nlp.device, dtype=torch.float64)
+        # torch.amin propagates NaN: a NaN margin fails, as in the audit
+        rows, sure = [], []
+        for comps in extrema_groups(spec):
+            sel = list(comps)
+            rows.append(var_margin[sel].amin(dim=0, keepdim=True) if sel else inf)
+            sure.append((var_margin[sel] - slack[sel]).amin(dim=0, keepdim=True) if sel else inf)
+        rows.append(mn[nv:nv + 1] if spec.param else inf)
+        sure.append(mn[nv:nv + 1] - slack[nv:nv + 1] if spec.param else inf)
+        margin, sure = torch.cat(rows).T.contiguous(), torch.cat(sure).T
+        passed = (margin >= -float(tol)).all(dim=1)
+        certified = (sure >= -float(tol)).all(dim=1) & (flag == 0).all(dim=0)
+        return ExtremaResult(val=val, var_margin=var_margin, margin=margin, overshoot=(-var_margin).clamp_min(0.0),
+                             passed=passed, certified=certified, tol=float(tol))

@@ -255,6 +255,31 @@ class BatchedNLP:
                                 stream=st.cuda_stream)
         return val
 
+    def extrema(self, W=None, intervals: bool = False, stream=None):
+        '''
+        The minimum and maximum of every node-vector component over WHOLE intervals, with a rigorous enclosure
+        (ato_extrema, asynchronous on `stream`): Bernstein branch and bound on the collocation polynomial itself,
+        no samples. W as in replay(). Channels v < NV are the components (z, u, du); parametric problems add
+        channel NV, s' = p_0'(x) / h_n (NVX = NV + 1). Returns (val, ival): val in the layout, interleaved
+        (NCH, NVX, B), instance-major (B, NVX, NCH), the eight channels (min, n, x, max, n, x, slack, flag) of
+        include/ato.h; ival the per-interval min and max, (NVX, N, 2, B) or (B, NVX, N, 2), None unless
+        `intervals`. One stream per problem handle. RK4-transcribed problems raise NotImplementedError.
+        '''
+        sp_, B = self.spec, self.batch
+        il = self.layout == native.ATO_LAYOUT_INTERLEAVED
+        W = self._columns(W, 'extrema')
+        nvx = sp_.nv + (1 if sp_.param else 0)
+        nch = native.ATO_EXTREMA_NCH
+        opts = {'device': self.device, 'dtype': torch.float64}
+        val = torch.empty((nch, nvx, B) if il else (B, nvx, nch), **opts)
+        ival = torch.empty((nvx, sp_.N, 2, B) if il else (B, nvx, sp_.N, 2), **opts) if intervals else None
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if stream is not None:      # a temporary made on the current stream, read on another
+            W.record_stream(st)
+        self.problem.extrema_ptrs(B, W.data_ptr(), val.data_ptr(), ival.data_ptr() if intervals else 0,
+                                  layout=self.layout, stream=st.cuda_stream)
+        return val, ival
+
     def set_gates(self, planes: Optional[dict]):
         ''' the gates gatecheck() checks: {'centre' (G, 3), 'R' (G, 3, 3), 'd_max' (G,), 'shape' (G,)} as
         raceline.gates.gate_planes returns them (at most 64, copied); None: the problem's own '''

@@ -147,6 +147,18 @@ class _Raceline:
         from aircraft_trajectory_optimization_amd.raceline.audit import audit_solutions
         return audit_solutions(self.spec, self._solution_vector(results)[None], samples=samples, varying='outer')
 
+    def extrema(self, results=None, tol: float = 1e-6):
+        '''
+        Certify the variable bounds and s' >= 0 of a solution of this problem over whole intervals on the device
+        (raceline/audit.py extrema_solutions): the exact extrema of every node-vector component's polynomial, not
+        samples of it. `results` as in audit(). Returns the ExtremaResult of that one instance, held to this
+        problem's own bounds (where a bound differs between nodes, to the loosest of them). RK4 transcriptions
+        raise NotImplementedError.
+        '''
+        from aircraft_trajectory_optimization_amd.raceline.audit import extrema_solutions, path_bounds
+        lb, ub = path_bounds(self.spec, varying='outer')
+        return extrema_solutions(self.spec, self._solution_vector(results)[None], tol=tol, lb=lb, ub=ub)
+
     def gate_passage(self, results=None, samples: int = 16, tol: float = 0.0):
         '''
         Passage of a solution of this problem through its gates on the device (raceline/gates.py): where and when

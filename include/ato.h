@@ -433,6 +433,37 @@ int ato_gatecheck_launches(ato_handle* h, int32_t batch, int32_t layout, const d
 int ato_export(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t n_times, const double* times,
                int32_t relative, double* nodes, double* state, void* stream);
 
+/* Extrema of collocation solutions over whole intervals (csrc/ato_extrema.hpp): per instance b and channel v the
+ * minimum and maximum, over all N intervals and every x in [0, 1], of p_{n,v}(x) = sum_j l_j(x) V[n, j, v] for
+ * v < NV (every per-node variable: states, inputs, input rates) and, in parametric problems, of p_{n,0}'(x) / h_n
+ * for v = NV (the audit's sdot). NVX = NV + 1 when parametric, else NV. The K + 1 node values are converted to
+ * Bernstein coefficients and a branch and bound over dyadic boxes encloses both extrema to a stop width of
+ * 2^-44 max(1, largest coefficient); the winning abscissae are re-evaluated through the Lagrange form, so min and
+ * max are values ato_audit would report there. Per (v, b) ATO_EXTREMA_NCH doubles:
+ *   0  min      the smallest value attained at a point the search evaluated
+ *   1, 2        its interval n and abscissa x (ties to the earliest (n, x))
+ *   3  max      the largest attained value
+ *   4, 5        its interval n and abscissa x
+ *   6  slack    >= 0: the true minimum is >= min - slack and the true maximum is <= max + slack, rounding of the
+ *               conversion, the subdivision and the re-evaluation included
+ *   7  flag     0; 1: the visit cap was hit in some interval (slack then holds that interval's root bounds);
+ *               NaN: a non-finite node value or coefficient (it never becomes an extremum), for channel NV also an
+ *               h_n that is not finite and positive
+ * Without any accepted interval min = +inf, max = -inf, n = -1 and x = NaN. val: channel c of (v, b) at
+ * [(c NVX + v) batch + b] (interleaved) or [(b NVX + v) ATO_EXTREMA_NCH + c] (instance-major). ival (or NULL): the
+ * min and max of every interval, [NVX][N][2][batch] (interleaved) or [batch][NVX][N][2]; NaN for a rejected
+ * interval. One launch, or two when the lap is split over blocks to fill the device at small batches; the partial
+ * records then live in a buffer on the handle, grown only when a call needs more: ONE stream per handle. No
+ * atomics, no device-wide synchronisation: bitwise repeatable, independent of the batch. CPC progress variables are
+ * not read; no centreline table is needed. Not covered: the audit's channels 7-13 (not polynomial). ATO_ERR_UNSUPPORTED:
+ * RK4 transcription; ATO_ERR_ARG: batch < 1, unknown layout, NULL w or val; nothing is launched or written then. */
+#define ATO_EXTREMA_NCH 8
+int ato_extrema(ato_handle* h, int32_t batch, int32_t layout, const double* w, double* val, double* ival,
+                void* stream);
+/* The Lagrange -> Bernstein table ato_extrema applies, T[i][j] row-major [K1][K1] for the abscissae tau[0 .. K1 - 1]
+ * (2 <= K1 <= 10): host only, no device is touched. */
+int ato_extrema_table(const double* tau, int32_t K1, double* T);
+
 /* Per-kernel timing with HIP events recorded on the evaluation stream. ato_timing(h, n)
  * allocates n event slots and starts recording (n = 0 stops); while on, each ato_eval
  * records events around its Jacobian kernel and its cost-reduction kernel. ato_timing_read

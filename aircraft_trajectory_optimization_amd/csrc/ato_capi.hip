@@ -761,6 +761,58 @@ extern "C" int ato_export(ato_handle* h, int32_t batch, int32_t layout, const do
     ATO_NOEXCEPT_BODY(export_impl(h, batch, layout, w, n_times, times, relative, nodes, state, stream))
 }
 
+static int compare_sample_impl(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t count,
+                               double* pos, double* lap, void* stream) {
+    if (!h) return fail(ATO_ERR_ARG, "null handle");
+    const ato::ProbD& p = h->pd;
+    const char* msg = "";
+    if (int rc = ato::compare_sample_check(p, h->d_line != nullptr, batch, layout, count, w != nullptr, pos != nullptr,
+                                           &msg))
+        return fail(rc, msg);
+    if (int rc = grow(&h->d_export_ts, &h->export_ts_len, (size_t)(p.N + 1) * batch,
+                      "comparison start times: out of device memory"))
+        return rc;
+    // the export's arguments at `count` fractions of the lap; the fractions are formed in the kernel, no time array
+    const ato::ExportD a = ato::export_args(p, count, 1, h->d_gate_tau, h->d_export_D, nullptr, h->d_export_ts, h->line);
+    hipError_t e = hipErrorInvalidValue;
+    ato::with_model(p, [&]<class M>() {
+        e = ato::launch_compare_sample<M>(a, batch, layout, w, pos, lap, (hipStream_t)stream);
+    });
+    if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("comparison sample launch: ") + hipGetErrorString(e));
+    return ATO_OK;
+}
+
+extern "C" int ato_compare_sample(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t count,
+                                  double* pos, double* lap, void* stream) {
+    ATO_NOEXCEPT_BODY(compare_sample_impl(h, batch, layout, w, count, pos, lap, stream))
+}
+
+extern "C" int ato_compare_pairs(ato_handle* h, int32_t count, int32_t bx, const double* px, int32_t by,
+                                 const double* py, int32_t metric, double eps, double* val, uint64_t* adj,
+                                 void* stream) {
+    (void)h;        // no problem is read: the tables are the input
+    const char* msg = "";
+    if (int rc = ato::compare_pairs_check(count, bx, px != nullptr, by, py == nullptr, metric, eps, val != nullptr,
+                                          adj != nullptr, &msg))
+        return fail(rc, msg);
+    const hipError_t e = ato::launch_compare_pairs(count, bx, px, by, py, metric, eps, val, (unsigned long long*)adj,
+                                                   (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("comparison pair launch: ") + hipGetErrorString(e));
+    return ATO_OK;
+}
+
+extern "C" int ato_compare_groups(ato_handle* h, int32_t batch, const uint64_t* adj, int32_t* group, int32_t* info,
+                                  void* stream) {
+    (void)h;
+    const char* msg = "";
+    if (int rc = ato::compare_groups_check(batch, adj != nullptr, group != nullptr, info != nullptr, &msg))
+        return fail(rc, msg);
+    const hipError_t e =
+        ato::launch_compare_groups(batch, (const unsigned long long*)adj, group, info, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("comparison groups launch: ") + hipGetErrorString(e));
+    return ATO_OK;
+}
+
 static int extrema_impl(ato_handle* h, int32_t batch, int32_t layout, const double* w, double* val, double* ival,
                         void* stream) {
     if (!h) return fail(ATO_ERR_ARG, "null handle");

@@ -12,6 +12,7 @@
 #include "ato_warmstart.hpp"
 #include "ato_export.hpp"
 #include "ato_extrema.hpp"
+#include "ato_compare.hpp"
 
 // A Lagrange weight table on the device, keyed by a substep or sample count. dev is allocated once (ato_create,
 // sized for the largest key) and holds the table of the key last uploaded; the host tables it is uploaded from

@@ -24,6 +24,8 @@ ATO_GATECHECK_NCH = 9   # channels per (gate, instance) of ato_gatecheck
 GATE_MAX = 64           # gates per ato_gatecheck call
 ATO_EXPORT_NCH = 30     # channels per (time, instance) of ato_export's state table
 ATO_EXTREMA_NCH = 8     # channels per (variable, instance) of ato_extrema
+ATO_COMPARE_NCH = 3     # channels per pair of ato_compare_pairs: rms, max, lap fraction of the max
+ATO_COMPARE_GROUP_MAX = 16382   # instances ato_compare_groups labels in LDS at the most
 ATO_OK, ATO_ERR_ARG, ATO_ERR_UNSUPPORTED, ATO_ERR_HIP, ATO_ERR_STATE = 0, -1, -2, -3, -4
 ABI_VERSION = 3
 CPC_MAX = 16                 # ATO_CPC_MAX
@@ -164,7 +166,8 @@ EXPORTED_SYMBOLS = ('ato_create', 'ato_destroy', 'ato_sizes', 'ato_sparsity', 'a
                     'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided', 'ato_clearance_set_line',
                     'ato_clearance', 'ato_audit', 'ato_gatecheck', 'ato_gatecheck_set_gates',
                     'ato_gatecheck_launches', 'ato_warmstart', 'ato_export', 'ato_extrema',
-                    'ato_extrema_table') + IPM_SYMBOLS
+                    'ato_extrema_table', 'ato_compare_sample', 'ato_compare_pairs',
+                    'ato_compare_groups') + IPM_SYMBOLS
 
 
 def library_path() -> str:
@@ -209,6 +212,10 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
         lib.ato_export.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, vp]
         lib.ato_extrema.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp]
         lib.ato_extrema_table.argtypes = [_c_double_p, ctypes.c_int32, _c_double_p]
+        lib.ato_compare_sample.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, vp]
+        lib.ato_compare_pairs.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32,
+                                          ctypes.c_double, vp, vp, vp]
+        lib.ato_compare_groups.argtypes = [vp, ctypes.c_int32, vp, vp, vp, vp]
         lib.ato_clearance_set_line.argtypes = [vp, ctypes.POINTER(AtoLineTable)]
         lib.ato_clearance.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp,
                                       ctypes.c_int32, vp]
@@ -263,7 +270,7 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
                    'ato_replay_set_lift', 'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided',
                    'ato_clearance_set_line', 'ato_clearance', 'ato_audit', 'ato_gatecheck',
                    'ato_gatecheck_set_gates', 'ato_gatecheck_launches', 'ato_warmstart', 'ato_export', 'ato_extrema',
-                   'ato_extrema_table'):
+                   'ato_extrema_table', 'ato_compare_sample', 'ato_compare_pairs', 'ato_compare_groups'):
             getattr(lib, fn).restype = ctypes.c_int
     return lib
 
@@ -635,6 +642,21 @@ class NativeProblem:
         rc = self.extrema_rc(batch, w, val, ival, layout, stream)
         self._check_supported(rc)
 
+    def compare_sample_rc(self, batch: int, w: int, count: int, pos: int, lap: int = 0,
+                          layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0) -> int:
+        ''' ato_compare_sample on device pointers; returns the library's code (ato_last_error has the message) '''
+        return self.lib.ato_compare_sample(self.handle, int(batch), int(layout), w or None, int(count), pos or None,
+                                           lap or None, stream or None)
+
+    def compare_sample_ptrs(self, batch: int, w: int, count: int, pos: int, lap: int = 0,
+                            layout: int = ATO_LAYOUT_INTERLEAVED, stream: int = 0):
+        '''
+        Global positions of the decision vectors w at `count` equal fractions of every instance's own lap
+        (asynchronous on `stream`; include/ato.h ato_compare_sample): pos [3 x count x batch], lap (or 0) [batch].
+        RK4-transcribed problems raise NotImplementedError with the library's message.
+        '''
+        self._check_supported(self.compare_sample_rc(batch, w, count, pos, lap, layout, stream))
+
     def timing_start(self, max_calls: int):
         ''' record HIP events around the kernels of the next max_calls evaluations '''
         self._check(self.lib.ato_timing(self.handle, int(max_calls)))
@@ -660,6 +682,19 @@ class NativeProblem:
             self.close()
         except Exception:  # pylint: disable=broad-except
             pass
+
+
+def compare_pairs_rc(count: int, bx: int, px: int, by: int = 0, py: int = 0, metric: int = 0, eps: float = 0.0,
+                     val: int = 0, adj: int = 0, stream: int = 0) -> int:
+    ''' ato_compare_pairs on device pointers (no problem handle: the tables are the input); returns the library's
+    code (ato_last_error has the message) '''
+    return load().ato_compare_pairs(None, int(count), int(bx), px or None, int(by), py or None, int(metric),
+                                    float(eps), val or None, adj or None, stream or None)
+
+
+def compare_groups_rc(batch: int, adj: int, group: int, info: int, stream: int = 0) -> int:
+    ''' ato_compare_groups on device pointers; returns the library's code (ato_last_error has the message) '''
+    return load().ato_compare_groups(None, int(batch), adj or None, group or None, info or None, stream or None)
 
 
 def extrema_table(tau) -> 'np.ndarray':

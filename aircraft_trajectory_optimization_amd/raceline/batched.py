@@ -345,6 +345,27 @@ class BatchedNLP:
                                  state.data_ptr(), layout=self.layout, stream=st.cuda_stream)
         return state, nod
 
+    def compare_sample(self, W=None, count: int = 64, stream=None):
+        '''
+        Global positions of decision vectors at `count` >= 2 equal fractions j / (count - 1) of every instance's
+        own lap (ato_compare_sample, asynchronous on `stream`): the export's position channels with `relative`,
+        three channels instead of thirty, the table raceline.compare feeds to the pair kernel. W as in audit().
+        Returns (pos, lap): (3, count, B) with the instance fastest whatever this batch's layout, and the lap times
+        (B,). One stream per problem handle: the start times are handle state, shared with export().
+        RK4-transcribed problems raise NotImplementedError.
+        '''
+        B = self.batch
+        W = self._columns(W, 'compare_sample')
+        self._ensure_line()
+        opts = {'device': self.device, 'dtype': torch.float64}
+        pos, lap = torch.empty((3, int(count), B), **opts), torch.empty((B,), **opts)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if stream is not None:      # a temporary made on the current stream, read on another
+            W.record_stream(st)
+        self.problem.compare_sample_ptrs(B, W.data_ptr(), int(count), pos.data_ptr(), lap.data_ptr(),
+                                         layout=self.layout, stream=st.cuda_stream)
+        return pos, lap
+
     def remesh_from(self, src: 'BatchedNLP', W_src, cols=None, stream=None) -> torch.Tensor:
         '''
         Transfer decision vectors of the batch `src` (the same scenario on a coarser mesh: this N a multiple

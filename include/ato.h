@@ -464,6 +464,49 @@ int ato_extrema(ato_handle* h, int32_t batch, int32_t layout, const double* w, d
  * (2 <= K1 <= 10): host only, no device is touched. */
 int ato_extrema_table(const double* tau, int32_t K1, double* T);
 
+/* Comparison of solutions (csrc/ato_compare.hpp): which instances of a batch are the same line. Three steps.
+ *
+ * ato_compare_sample: the global position of every instance at `count` >= 2 equal fractions of its OWN lap,
+ * t = f_j T_b, f_j = (double)j / (double)(count - 1): ato_export's state channels 3-5 with relative != 0 at those
+ * fractions (the same interpolation, hold and lift; a non-finite node value gives NaN positions). pos:
+ * [3][count][batch], instance fastest, whatever `layout` of w. lap (or NULL): [batch], T_b, ato_export's sequential
+ * fp64 sum. Two launches; the start times live in ato_export's buffer on the handle: ONE stream per handle. The
+ * checks and codes of ato_export, in its order: ATO_ERR_ARG: batch < 1, unknown layout, count < 2, NULL w or pos;
+ * ATO_ERR_UNSUPPORTED: RK4 transcription; ATO_ERR_STATE: a parametric problem without its centreline table; nothing
+ * is launched or written then.
+ *
+ * ato_compare_pairs: px [3][count][bx] and py [3][count][by] are tables of ato_compare_sample, possibly of handles
+ * with different N and K; py == NULL compares px with itself (by is ignored, the result is bx x bx). No problem is read: h
+ * may be NULL, here and in ato_compare_groups; the tables live on the stream's device. For every pair (a, b), with d2_j = |px[:, j, a] - py[:, j, b]|^2 (three
+ * differences, then fused multiply-adds over x, y, z), ATO_COMPARE_NCH channels at val[(c bx + a) by + b]:
+ *   0  rms   sqrt((sum_j d2_j) / count), the sum sequential in ascending j
+ *   1  max   sqrt(max_j d2_j)
+ *   2  at    f_j of the earliest j whose d2_j attains the maximum
+ * A pair's numbers depend on its two columns alone (not on bx, by or the tiling) and do not change when the
+ * operands are swapped; a self-comparison is bitwise symmetric with an exactly zero diagonal for finite columns. A
+ * pair whose sum is not finite (a NaN or infinite position, an overflow) has NaN in all channels and no adjacency.
+ * adj (or NULL): [bx][ceil(by / 64)] words, bit (b & 63) of word [a][b >> 6] set iff the metric (0: max, 1: rms)
+ * is <= eps (eps >= 0); padding bits are zero. val may be NULL when only the bits are wanted. One launch, no
+ * atomics on global memory, no scratch. ATO_ERR_ARG: count < 2, bx < 1, by < 1 with py, NULL px, val and adj both
+ * NULL, unknown metric, eps negative or NaN with adj; nothing is launched or written then.
+ *
+ * ato_compare_groups: adj is a square [batch][ceil(batch / 64)] matrix of ato_compare_pairs; group[b] is the
+ * smallest instance index of b's connected component in the union of adj and its transpose (single linkage). One
+ * launch of one workgroup with the labels in LDS; at most `batch` sweeps of min-label propagation and pointer
+ * jumping, which is provably enough (the diameter is at most batch - 1). info[0]: the sweeps run; info[1]: 1 if
+ * that cap ended the loop (never, for a matrix of `batch` rows), else 0. Bits at or beyond `batch` are ignored.
+ * ATO_ERR_ARG: batch < 1, NULL adj, group or info; ATO_ERR_UNSUPPORTED: batch > 16382 (64 kB of labels); nothing
+ * is launched or written then.
+ * Not covered: alignment in space (one path at two speed profiles is two solutions), anything but position, RK4,
+ * fp32. It certifies nothing. */
+#define ATO_COMPARE_NCH 3
+int ato_compare_sample(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t count, double* pos,
+                       double* lap, void* stream);
+int ato_compare_pairs(ato_handle* h, int32_t count, int32_t bx, const double* px, int32_t by, const double* py,
+                      int32_t metric, double eps, double* val, uint64_t* adj, void* stream);
+int ato_compare_groups(ato_handle* h, int32_t batch, const uint64_t* adj, int32_t* group, int32_t* info,
+                       void* stream);
+
 /* Per-kernel timing with HIP events recorded on the evaluation stream. ato_timing(h, n)
  * allocates n event slots and starts recording (n = 0 stops); while on, each ato_eval
  * records events around its Jacobian kernel and its cost-reduction kernel. ato_timing_read

@@ -813,6 +813,20 @@ extern "C" int ato_compare_groups(ato_handle* h, int32_t batch, const uint64_t* 
     return ATO_OK;
 }
 
+extern "C" int ato_compare_path(ato_handle* h, int32_t count, int32_t bx, const double* px, int32_t by,
+                                const double* py, int32_t metric, double eps, double* val, uint64_t* adj,
+                                void* stream) {
+    (void)h;        // no problem is read: the tables are the input
+    const char* msg = "";
+    if (int rc = ato::compare_pairs_check(count, bx, px != nullptr, by, py == nullptr, metric, eps, val != nullptr,
+                                          adj != nullptr, &msg))
+        return fail(rc, msg);
+    const hipError_t e = ato::launch_compare_path(count, bx, px, by, py, metric, eps, val, (unsigned long long*)adj,
+                                                  (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ATO_ERR_HIP, std::string("comparison path launch: ") + hipGetErrorString(e));
+    return ATO_OK;
+}
+
 static int extrema_impl(ato_handle* h, int32_t batch, int32_t layout, const double* w, double* val, double* ival,
                         void* stream) {
     if (!h) return fail(ATO_ERR_ARG, "null handle");

@@ -33,8 +33,9 @@
 // threads race on intermediate labels (LDS atomic minima and plain reads); the fixpoint -- no edge joins two
 // labels, every label its component's minimum -- is unique, so the output does not depend on the race.
 //
-// Not covered: an alignment in space (two lines on one path with different speed profiles are different here),
-// anything but position, RK4 transcriptions. It certifies nothing.
+// Not covered here: an alignment in space -- two lines on one path with different speed profiles are different to
+// the pair kernel; ato_path.hpp (ato_compare_path) compares the same tables as paths and feeds the same groups.
+// Not covered at all: anything but position, the curve between the samples, RK4 transcriptions. It certifies nothing.
 #pragma once
 #include "ato_export.hpp"
 

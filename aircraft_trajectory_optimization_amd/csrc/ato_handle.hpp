@@ -13,6 +13,7 @@
 #include "ato_export.hpp"
 #include "ato_extrema.hpp"
 #include "ato_compare.hpp"
+#include "ato_path.hpp"
 
 // A Lagrange weight table on the device, keyed by a substep or sample count. dev is allocated once (ato_create,
 // sized for the largest key) and holds the table of the key last uploaded; the host tables it is uploaded from

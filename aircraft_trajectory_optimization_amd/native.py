@@ -25,6 +25,7 @@ GATE_MAX = 64           # gates per ato_gatecheck call
 ATO_EXPORT_NCH = 30     # channels per (time, instance) of ato_export's state table
 ATO_EXTREMA_NCH = 8     # channels per (variable, instance) of ato_extrema
 ATO_COMPARE_NCH = 3     # channels per pair of ato_compare_pairs: rms, max, lap fraction of the max
+ATO_COMPARE_PATH_NCH = 8    # channels per pair of ato_compare_path: rms, max, at, where of a -> b, then of b -> a
 ATO_COMPARE_GROUP_MAX = 16382   # instances ato_compare_groups labels in LDS at the most
 ATO_OK, ATO_ERR_ARG, ATO_ERR_UNSUPPORTED, ATO_ERR_HIP, ATO_ERR_STATE = 0, -1, -2, -3, -4
 ABI_VERSION = 3
@@ -167,7 +168,7 @@ EXPORTED_SYMBOLS = ('ato_create', 'ato_destroy', 'ato_sizes', 'ato_sparsity', 'a
                     'ato_clearance', 'ato_audit', 'ato_gatecheck', 'ato_gatecheck_set_gates',
                     'ato_gatecheck_launches', 'ato_warmstart', 'ato_export', 'ato_extrema',
                     'ato_extrema_table', 'ato_compare_sample', 'ato_compare_pairs',
-                    'ato_compare_groups') + IPM_SYMBOLS
+                    'ato_compare_groups', 'ato_compare_path') + IPM_SYMBOLS
 
 
 def library_path() -> str:
@@ -216,6 +217,7 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
         lib.ato_compare_pairs.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32,
                                           ctypes.c_double, vp, vp, vp]
         lib.ato_compare_groups.argtypes = [vp, ctypes.c_int32, vp, vp, vp, vp]
+        lib.ato_compare_path.argtypes = lib.ato_compare_pairs.argtypes
         lib.ato_clearance_set_line.argtypes = [vp, ctypes.POINTER(AtoLineTable)]
         lib.ato_clearance.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp, vp,
                                       ctypes.c_int32, vp]
@@ -270,7 +272,8 @@ def declare(lib: ctypes.CDLL, prefix: str = 'ato') -> ctypes.CDLL:
                    'ato_replay_set_lift', 'ato_replay', 'ato_remesh', 'ato_mesh_signed_distance_strided',
                    'ato_clearance_set_line', 'ato_clearance', 'ato_audit', 'ato_gatecheck',
                    'ato_gatecheck_set_gates', 'ato_gatecheck_launches', 'ato_warmstart', 'ato_export', 'ato_extrema',
-                   'ato_extrema_table', 'ato_compare_sample', 'ato_compare_pairs', 'ato_compare_groups'):
+                   'ato_extrema_table', 'ato_compare_sample', 'ato_compare_pairs', 'ato_compare_groups',
+                   'ato_compare_path'):
             getattr(lib, fn).restype = ctypes.c_int
     return lib
 
@@ -690,6 +693,14 @@ def compare_pairs_rc(count: int, bx: int, px: int, by: int = 0, py: int = 0, met
     code (ato_last_error has the message) '''
     return load().ato_compare_pairs(None, int(count), int(bx), px or None, int(by), py or None, int(metric),
                                     float(eps), val or None, adj or None, stream or None)
+
+
+def compare_path_rc(count: int, bx: int, px: int, by: int = 0, py: int = 0, metric: int = 0, eps: float = 0.0,
+                    val: int = 0, adj: int = 0, stream: int = 0) -> int:
+    ''' ato_compare_path on device pointers, the arguments of compare_pairs_rc (val: 8 planes); returns the
+    library's code (ato_last_error has the message) '''
+    return load().ato_compare_path(None, int(count), int(bx), px or None, int(by), py or None, int(metric),
+                                   float(eps), val or None, adj or None, stream or None)
 
 
 def compare_groups_rc(batch: int, adj: int, group: int, info: int, stream: int = 0) -> int:

@@ -497,15 +497,41 @@ int ato_extrema_table(const double* tau, int32_t K1, double* T);
  * that cap ended the loop (never, for a matrix of `batch` rows), else 0. Bits at or beyond `batch` are ignored.
  * ATO_ERR_ARG: batch < 1, NULL adj, group or info; ATO_ERR_UNSUPPORTED: batch > 16382 (64 kB of labels); nothing
  * is launched or written then.
- * Not covered: alignment in space (one path at two speed profiles is two solutions), anything but position, RK4,
- * fp32. It certifies nothing. */
+ *
+ * ato_compare_path: the same tables compared as PATHS (csrc/ato_path.hpp), which ato_compare_pairs is not: there one
+ * path at two speed profiles is two solutions. Line b is the polyline through its `count` samples (count - 1
+ * segments; a closed lap closes by itself because f = 1 repeats f = 0). For point p and segment (q0, q1):
+ *   e = q1 - q0, r = p - q0, inv = 1 / (e.e), raised by one ulp where (e.e) inv rounds below 1 (the far vertex then
+ *   projects to t = 1 exactly), and 0 where e.e == 0; t = clamp((r.e) inv, 0, 1); c = r - t e by fused
+ *   multiply-adds; d2 = c.c; the dot products are fused multiply-adds in the fixed order z, y, x.
+ * The directed record of (a -> b):
+ *   D_i   = min over the segments s of b, in ascending s, the first of equals, of d2(px[:, i, a], segment s)
+ *   rms   = sqrt((sum_i D_i) / count), the sum sequential in ascending i
+ *   max   = sqrt(max_i D_i)
+ *   at    = f_i of the earliest i attaining the maximum
+ *   where = (s* + t*) / (count - 1): the lap fraction ON b of the point nearest to that sample; where - at is the
+ *           timing lag at the worst point
+ * ATO_COMPARE_PATH_NCH channels at val[(c bx + a) by + b]: 0-3 are rms, max, at, where of a -> b, 4-7 those of
+ * b -> a. The Hausdorff distance is max(ch 1, ch 5). adj as in ato_compare_pairs, the bit being "metric(a -> b) <=
+ * eps AND metric(b -> a) <= eps" with the directed max (metric 0) or the directed rms (1). A pair whose sum is not
+ * finite in either direction has NaN in all eight channels and no bit. A pair's numbers depend on its two columns
+ * alone: not on bx, by, the tiling, or the side a column is on; a self-comparison (py == NULL) has an exactly zero
+ * diagonal and val[c][a][b] == val[4 + c][b][a] bit for bit. Arguments, checks and codes are those of
+ * ato_compare_pairs (h may be NULL; nothing is launched or written on an error). One launch, no atomics on global
+ * memory, no scratch. Error bound in csrc/ato_path.hpp.
+ *
+ * Not covered: ato_compare_pairs aligns nothing in space (ato_compare_path does); anything but position, the curve
+ * between the samples (ato_compare_path measures against the polyline), RK4, fp32. It certifies nothing. */
 #define ATO_COMPARE_NCH 3
+#define ATO_COMPARE_PATH_NCH 8
 int ato_compare_sample(ato_handle* h, int32_t batch, int32_t layout, const double* w, int32_t count, double* pos,
                        double* lap, void* stream);
 int ato_compare_pairs(ato_handle* h, int32_t count, int32_t bx, const double* px, int32_t by, const double* py,
                       int32_t metric, double eps, double* val, uint64_t* adj, void* stream);
 int ato_compare_groups(ato_handle* h, int32_t batch, const uint64_t* adj, int32_t* group, int32_t* info,
                        void* stream);
+int ato_compare_path(ato_handle* h, int32_t count, int32_t bx, const double* px, int32_t by, const double* py,
+                     int32_t metric, double eps, double* val, uint64_t* adj, void* stream);
 
 /* Per-kernel timing with HIP events recorded on the evaluation stream. ato_timing(h, n)
  * allocates n event slots and starts recording (n = 0 stops); while on, each ato_eval

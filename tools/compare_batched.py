@@ -4,10 +4,11 @@ the race track) as bench.py --full --dump-outputs DIR wrote it (x.npy, status.np
 equal fractions of its own lap, compares all pairs (raceline/compare.py) and reports: the number of distinct lines
 at --eps (5 cm) among all columns and among the optimal ones, the sizes of the groups and the lap time of each
 group's representative (its fastest optimal member), and how many max_iter columns lie within eps of an optimal one.
-Without --dir it runs that solve itself (--batch seeded cold starts under --max-iter).
+Without --dir it runs that solve itself (--batch seeded cold starts under --max-iter). --metric path_max / path_rms
+compares the columns as paths (ato_compare_path): "distinct lines" then are distinct paths, whatever the speed profile.
 
     python tools/compare_batched.py [--dir DIR | --batch 512 --max-iter 1000] [--count 64] [--eps 0.05]
-                                    [--metric max] [--out f.json]
+                                    [--metric max|rms|path_max|path_rms] [--out f.json]
 '''
 import argparse
 import json
@@ -28,7 +29,7 @@ def main():
     ap.add_argument('--max-iter', type=int, default=1000)
     ap.add_argument('--count', type=int, default=64)
     ap.add_argument('--eps', type=float, default=0.05)
-    ap.add_argument('--metric', choices=('max', 'rms'), default='max')
+    ap.add_argument('--metric', choices=('max', 'rms', 'path_max', 'path_rms'), default='max')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     from aircraft_trajectory_optimization_amd.raceline.compare import compare_solutions
